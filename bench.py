@@ -11,13 +11,24 @@ the whole window's average whatever K is (the decode attention's cost grows
 with the position).  Weights and KV cache are resident in HBM before the timed
 region.
 
-Also reported on the same line:
+A plain run (--gpus 1 --steps K --warmup W) does only that: it loads the model,
+warms up, times the K steps, writes the last timed step's outputs when
+--dump-outputs DIR is given, and prints the result line.
+
+--dump-outputs DIR writes what the timed path returned in its last step, the
+logits row llama_get_logits holds after that llama_eval, as DIR/logits.npy
+(float32 [1, n_vocab]).  Model, prompt and positions are seeded and fixed, so
+the same arguments give the same inputs on every run and build.
+
+--full adds, on the same line:
   prompt_eval   one 512-token llama_eval (BASELINE.json configs[2]), best of 3
   roofline      dominant kernel's algorithmic weight bytes per launch / its
                 average duration, HIP events on the launch stream (profiled
                 decode pass right after the timed region)
   cpu_baseline  the reference AVX2 ggml.c build (oracle/_ref, compiled from
                 /root/reference) on the same file, host cores, bounded sample
+and the device-sampler, 13B Q4_1, 65B Q4_0 and (N > 1) layer-split legs with
+their correctness checks.
 
 Multi-GPU (torchrun): the 7B model does not shard: every rank
 runs an independent replica; value = total tokens of all ranks / max time.
@@ -575,6 +586,11 @@ def main():
     ap.add_argument("--steps", type=int, default=496)
     ap.add_argument("--warmup", type=int, default=16)
     ap.add_argument("--model", default="/tmp/lvk_bench/llama-7b-q4_0.bin")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg (device sampler, prompt eval, per-kernel profile and roofline, "
+                         "13B / 65B / layer-split lines, stream checks, CPU baselines); off: the timed 7B decode only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's logits row to DIR/logits.npy (float32)")
     ap.add_argument("--prompt-evals", type=int, default=3)
     ap.add_argument("--profile-steps", type=int, default=48)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -627,7 +643,8 @@ def main():
 
 
 def run(args, coord):
-    """every leg of the bench on this rank's GPU; returns rank 0's JSON object (None elsewhere)"""
+    """the timed 7B decode, and with --full every other leg, on this rank's GPU; returns rank 0's
+    JSON object (None elsewhere)"""
     ws, rank, local = coord.ws, coord.rank, coord.local
     if args.coord_selftest:
         # the N > 1 plumbing without a GPU (tests/test_bench_coord.py): no lvk, no torch here
@@ -687,6 +704,13 @@ def run(args, coord):
     positions = ("16..511, each once in order" if args.steps == win else
                  "spread evenly over 16..511 (window filled first)" if args.steps < win else
                  "16..511 wrapping to 16 after 511")
+    if args.dump_outputs and rank == 0:
+        # lg is a view of the context's host buffer: written before anything evaluates again
+        dump_outputs(args.dump_outputs, {"logits": lg})
+
+    if not args.full:
+        m.close()
+        return result_line(args, n_gpus, value, elapsed, positions, n_ctx, load_s) if rank == 0 else None
 
     greedy = None
     if not args.no_greedy:
@@ -823,7 +847,6 @@ def run(args, coord):
     roofline = {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                 "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "bytes_per_launch": bpl,
                 "avg_launch_us": avg_s * 1e6}
-    step_gbs = value / n_gpus * MODEL_BYTES_7B / 1e9
 
     # 13B Q4_1 single-stream decode (BASELINE.json configs[3]), same loop
     m.close()          # one model resident at a time from here on
@@ -897,24 +920,10 @@ def run(args, coord):
 
     if rank != 0:
         return None
-    out = {
-        "metric": "decode tok/s + prompt-eval tok/s, LLaMA-7B Q4_0; % HBM roofline",
-        "value": value, "unit": "tok/s", "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": value / REF_PUBLISHED_TOKS,
-        "vs_baseline_note": "vs_baseline divides by the README's published 7B Q4_0 CPU figure (16.3 tok/s, Apple "
-                            "Silicon, BASELINE.md section 1); vs_cpu_baseline divides by the reference build timed "
-                            "on this box's host cores in this run (cpu_baseline)",
+    out = result_line(args, n_gpus, value, elapsed, positions, n_ctx, load_s)
+    out.update({
         "vs_cpu_baseline": (value / n_gpus / cpu["value"]) if cpu else None,
-        "dtype": "i4xi4->f32 (Q4_0 blocks, exact int dots, fp32 FMA chains)",
-        "data": "synthetic (seeded ggjt 7B Q4_0, lvk-gen-model seed 1)",
-        "config": {"workload": "LLaMA-7B Q4_0 single-stream decode: 16-token prompt then %d greedy decode "
-                               "steps at positions %s, n_ctx 512, f16 KV" % (args.steps, positions),
-                   "n_ctx": n_ctx,
-                   "parallelism": "replicas" if n_gpus > 1 else "single-gpu"},
         "roofline": roofline,
-        "step_roofline": {"model_bytes_per_token": MODEL_BYTES_7B, "achieved_gbs": step_gbs,
-                          "frac": step_gbs / HBM_PEAK_GBS, "roofline_tok_s": HBM_PEAK_GBS * 1e9 / MODEL_BYTES_7B},
         "prompt_eval": prompt,
         "decode_greedy_device": greedy,
         "decode_13b_q4_1": q41,
@@ -922,10 +931,40 @@ def run(args, coord):
         "layer_split": split,
         "kernels": kernels,
         "cpu_baseline": cpu,
-        "load_s": load_s,
-    }
+    })
     out["checks"] = collect_checks(out)
     return out
+
+
+def result_line(args, n_gpus, value, elapsed, positions, n_ctx, load_s):
+    """the timed 7B decode's own fields: all a plain run prints; --full adds its legs to them"""
+    step_gbs = value / n_gpus * MODEL_BYTES_7B / 1e9
+    return {
+        "metric": "decode tok/s + prompt-eval tok/s, LLaMA-7B Q4_0; % HBM roofline",
+        "value": value, "unit": "tok/s", "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "full": args.full,
+        "scaling": "weak", "vs_baseline": value / REF_PUBLISHED_TOKS,
+        "vs_baseline_note": "vs_baseline divides by the README's published 7B Q4_0 CPU figure (16.3 tok/s, Apple "
+                            "Silicon, BASELINE.md section 1); vs_cpu_baseline (--full) divides by the reference "
+                            "build timed on the host cores in the same run (cpu_baseline)",
+        "dtype": "i4xi4->f32 (Q4_0 blocks, exact int dots, fp32 FMA chains)",
+        "data": "synthetic (seeded ggjt 7B Q4_0, lvk-gen-model seed 1)",
+        "config": {"workload": "LLaMA-7B Q4_0 single-stream decode: 16-token prompt then %d greedy decode "
+                               "steps at positions %s, n_ctx 512, f16 KV" % (args.steps, positions),
+                   "n_ctx": n_ctx,
+                   "parallelism": "replicas" if n_gpus > 1 else "single-gpu"},
+        "step_roofline": {"model_bytes_per_token": MODEL_BYTES_7B, "achieved_gbs": step_gbs,
+                          "frac": step_gbs / HBM_PEAK_GBS, "roofline_tok_s": HBM_PEAK_GBS * 1e9 / MODEL_BYTES_7B},
+        "load_s": load_s,
+    }
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: each array as DIR/<name>.npy, float32"""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), np.array(a, dtype=np.float32))
 
 
 def collect_checks(out):

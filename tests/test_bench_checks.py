@@ -30,6 +30,17 @@ def test_spread_positions_wrap_past_the_window(bench):
     assert pos[:496] == list(range(16, 512)) and pos[496] == 16
 
 
+def test_dump_outputs_writes_float32_npy(bench, tmp_path):
+    import numpy as np
+    row = np.arange(12, dtype=np.float64).reshape(1, 12) / 7
+    row.flags.writeable = False                               # the timed path hands out a read-only view
+    d = tmp_path / "new" / "dir"
+    bench.dump_outputs(str(d), {"logits": row})
+    got = np.load(str(d / "logits.npy"))
+    assert got.dtype == np.float32 and got.shape == (1, 12)
+    assert np.array_equal(got, row.astype(np.float32))
+
+
 def test_collect_checks_passes_when_every_check_holds(bench):
     out = {"decode_greedy_device": {"stream_check": {"digests_equal": True}, "chained": {"tokens_match_eval_greedy": True}},
            "decode_13b_q4_1": {"stream_check": {"digests_equal": True}}, "decode_65b_q4_0": None,

@@ -5,7 +5,7 @@ mkdir -p gpurun_out/meas
 export TMPDIR=/tmp
 O=gpurun_out/meas
 timeout -k 10 300 python3 tools/decode_speed.py 7b 8 > $O/gen7.log 2>&1 || exit 1
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/kt7 -o run --output-format csv -- python3 bench.py --steps 16 --warmup 4 --no-13b --no-65b --no-cpu-baseline --prompt-evals 1 > $O/kt7.log 2>&1 || exit 2
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/kt7 -o run --output-format csv -- python3 bench.py --full --steps 16 --warmup 4 --no-13b --no-65b --no-cpu-baseline --prompt-evals 1 > $O/kt7.log 2>&1 || exit 2
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/kt13 -o run --output-format csv -- python3 tools/decode_speed.py 13b 16 > $O/kt13.log 2>&1 || exit 3
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/kt65 -o run --output-format csv -- python3 tools/decode_speed.py 65b 16 > $O/kt65.log 2>&1 || exit 4
 timeout -s KILL 120 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_LDS SQ_WAIT_INST_ANY -d $O/pmcA -o run --output-format csv -- python3 tools/prompt_once.py > $O/pmcA.log 2>&1 || exit 5
