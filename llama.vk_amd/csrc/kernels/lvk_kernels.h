@@ -37,7 +37,8 @@ struct EventSplit {
             hipLaunchKernelGGL(kern, grid, block, lds, stream, __VA_ARGS__);                                   \
     } while (0)
 
-enum QType : int { Q4_0 = 2, Q4_1 = 3 };
+// = the model file's tensor type ids; F16 matrices use the paired-step octet image below
+enum QType : int { F16 = 1, Q4_0 = 2, Q4_1 = 3 };
 
 // error word: kernels whose workgroups wait on each other spin with a bound; a
 // spin that gives up stores one of these into the context's host-mapped error
@@ -53,6 +54,8 @@ enum DevError : unsigned { LVK_ERR_NONE = 0, LVK_ERR_ATTN_SPIN = 1, LVK_ERR_DECO
 //   scl : [M/8][NC][64]   float4  -- d of blocks 32c+8m+j, m = 0..3
 // Bytes per row equal the file's (20 B per 32 weights; the last chunk of a
 // row is zero-padded to 32 blocks when K % 1024 != 0 and never streamed).
+// F16 matrices: nib is the paired-step octet image [ceil(M/8)][K/64][64] uint4
+// (f16_common.h; f16_image_bytes, launch_repack_f16), scl is unused.
 struct QMatrix {
     int qtype = Q4_0;
     int M = 0, K = 0;
@@ -259,6 +262,21 @@ hipError_t launch_mm_w13_q(const QMatrix & w, const void * xm, const float * da,
 // RoPE + KV append of stored Q|K|V rows qkv [N][3E]
 hipError_t launch_rope_kv(const float * qkv, int N, int E, int hd, const float2 * rope, const StepParams * sp,
                           int n_ctx, uint16_t * q16, uint16_t * kc, uint16_t * vc, hipStream_t s, int kv32 = 0);
+
+// f16 weights (type 1).  Image: 2 B per weight, rows padded to a multiple of 8.
+inline size_t f16_image_bytes(int M, int K) { return (size_t) ((M + 7) / 8 * 8) * K * 2; }
+hipError_t launch_repack_f16(const void * src_rows, int M, int K, uint4 * img, hipStream_t s, int interleave4 = 0);
+// single-token decode matvec (matvec_f16.hip): PRO_NORM (rms_norm * g -> f16) or PRO_ACTF
+// (f32 -> f16) of the f32 row L.x; EPI_STORE, EPI_RESID, EPI_QKV, EPI_SWIGLU_F32
+hipError_t launch_matvec_f16(const MvLaunch & L, int pro, int epi, hipStream_t s);
+// batched matmul (mm_f16.hip): the activations' paired f16 rows x16 (mm_f16_act_bytes: N
+// rounded up to MM_F16_TPAD rows, any contents in the padding) from launch_act_f16p (g !=
+// nullptr: rms_norm * g first), then y[N][ldy] = / += W x, or u = silu(w1 x) * (w3 x)
+constexpr int MM_F16_TPAD = 32;
+size_t mm_f16_act_bytes(int N, int K);
+hipError_t launch_act_f16p(const float * x, const float * g, int N, int K, void * x16, hipStream_t s);
+hipError_t launch_mm_f16(const QMatrix & w, const void * x16, int N, float * y, int ldy, int epi,
+                         const uint16_t * silu_tab, hipStream_t s);
 
 // operator-level helpers used by the C ABI tests
 hipError_t launch_quantize_act(const float * x, int N, int K, int qtype, ActQ out, hipStream_t s);

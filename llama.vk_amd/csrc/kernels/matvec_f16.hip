@@ -1,0 +1,190 @@
+// matvec_f16.hip -- single-token W[M][K] . x for f16 weights, bit-identical to
+// ggml_compute_forward_mul_mat_f16_f32 (AVX2), plus the load-time repack of an f16 matrix
+// into its paired-step octet image (f16_common.h).
+//
+// One launch per matrix.  A workgroup of NW waves converts the activation row to f16 in LDS
+// (after RMSNorm * g for PRO_NORM), then every wave streams one 8-row group: 1 KiB per
+// global_load_dwordx4, D loads in flight per lane, 8 v_fma_mix_f32 per load against one
+// ds_read_b128 of the activation image.  The kernel is purely bandwidth-bound; no workgroup
+// waits on another.
+#include "f16_common.h"
+#include "matvec_common.h"
+
+namespace lvk {
+
+namespace {
+using namespace f16k;
+
+struct F16Params {
+    const uint4 * img;
+    int M, K, G;                // G = row groups, ceil(M / 8)
+    const float * x;            // f32 input row [K]
+    const float * g;            // PRO_NORM: norm weight [K]
+    const StepParams * sp;
+    float * y;                  // EPI_STORE / EPI_RESID row [M]
+    float * u;                  // EPI_SWIGLU_F32 [M / 2]
+    uint16_t * q16;
+    uint16_t * kc;
+    uint16_t * vc;
+    const float2 * rope;
+    int n_embd, head_dim, n_ctx, kv32;
+    const uint16_t * silu_tab;
+};
+
+constexpr int D = 16;           // 16-byte weight loads in flight per lane (16 KiB per wave)
+
+template <int NW, int PRO, int EPI>
+__global__ __launch_bounds__(NW * 64) void k_matvec_f16(F16Params P) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const int c = lane & 7;
+    const int r = lane >> 3;
+    const int K = P.K;
+    const int S = K / 64;                               // 16-byte units per lane and row
+    const int grp = blockIdx.x * NW + wave;
+    const bool live = grp < P.G;
+    const int nfull = S / D, R = S - nfull * D;
+
+    uint2 * xs2 = (uint2 *) smem;                       // 2 K bytes: the row's paired f16 image
+    double * red = (double *) (smem + (size_t) 2 * K);  // NW doubles
+
+    // the first D weight loads go out ahead of the prologue (they never depend on x)
+    const uint4 * wp = P.img + (size_t) (live ? grp : 0) * S * 64 + lane;
+    uint4 W[D];
+    if (nfull > 0) {
+#pragma unroll
+        for (int d = 0; d < D; ++d) W[d] = ld_nt(wp + (size_t) d * 64);
+    }
+
+    act_row_f16<NW * 64, PRO == PRO_NORM>(P.x, P.g, K, xs2, red);
+    if (!live) return;                                  // wave-uniform, after the last barrier
+
+    const uint4 * xs = (const uint4 *) smem + c;
+    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    int s0 = 0;
+    if (nfull > 0) {
+        for (int ch = 0; ch + 1 < nfull; ++ch, s0 += D) {
+#pragma unroll
+            for (int d = 0; d < D; ++d) {
+                fma8(acc, W[d], xs[(s0 + d) * 8]);
+                W[d] = ld_nt(wp + (size_t) (s0 + D + d) * 64);
+            }
+        }
+        // last full chunk; the remainder (R < D units) is loaded behind it
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+            fma8(acc, W[d], xs[(s0 + d) * 8]);
+            if (d < R) W[d] = ld_nt(wp + (size_t) (s0 + D + d) * 64);
+        }
+        s0 += D;
+#pragma unroll
+        for (int d = 0; d < D; ++d)
+            if (d < R) fma8(acc, W[d], xs[(s0 + d) * 8]);
+    } else {
+        for (int s = 0; s < S; ++s) fma8(acc, ld_nt(wp + (size_t) s * 64), xs[s * 8]);
+    }
+
+    const float res = chain_reduce(acc);
+    const int row = grp * 8 + r;
+    if constexpr (EPI == EPI_STORE) {
+        if (c == 0 && row < P.M) P.y[row] = res;
+    } else if constexpr (EPI == EPI_RESID) {
+        // ggml_add(cur, inpSA) (llama.cpp:1071,1103)
+        if (c == 0 && row < P.M) P.y[row] = res + P.y[row];
+    } else if constexpr (EPI == EPI_QKV) {
+        mv::qkv_epilogue(res, row, c, P.n_embd, P.head_dim, P.sp->n_past, P.rope, P.q16, P.kc, P.vc, P.n_ctx, P.kv32);
+    } else if constexpr (EPI == EPI_SWIGLU_F32) {
+        // fused W1|W3 image interleaved per 4 rows: rows 0-3 of the group are w1 rows
+        // 4grp .. 4grp+3, rows 4-7 the matching w3 rows (llama.cpp:1085-1096)
+        const float a3 = __shfl_xor(res, 32);
+        if (r < 4 && c == 0) {
+            const float sl = f16_to_f32(P.silu_tab[f32_to_f16(res)]);   // ggml_vec_silu_f32 (ggml.c:2495)
+            P.u[grp * 4 + r] = sl * a3;                                  // ggml_mul (llama.cpp:1096)
+        }
+    }
+}
+
+// file-layout f16 rows -> paired-step octet image, one thread per 16-byte unit.  Rows past M
+// (the last group of an M % 8 != 0 matrix) are zero.  interleave4: src holds two (M/2)-row
+// matrices A then B; image rows are A0-3, B0-3, A4-7, ... (the fused W1|W3)
+__global__ void k_repack_f16(const uint16_t * __restrict__ src, int M, int K, uint4 * __restrict__ img, int interleave4) {
+    const int S = K / 64;
+    const size_t total = (size_t) ((M + 7) / 8) * S * 64;
+    const size_t o = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (o >= total) return;
+    const int lane = (int) (o & 63);
+    const size_t gs = o >> 6;
+    const int s = (int) (gs % S);
+    const int grp = (int) (gs / S);
+    const int r = lane >> 3, c = lane & 7;
+    int row = grp * 8 + r;
+    if (interleave4) row = (r < 4 ? 0 : M / 2) + grp * 4 + (r & 3);
+    uint4 v = make_uint4(0, 0, 0, 0);
+    if (grp * 8 + r < M) {
+        const uint16_t * p = src + (size_t) row * K + (size_t) s * 64 + 4 * c;
+        const uint2 a = *(const uint2 *) p, b = *(const uint2 *) (p + 32);
+        v = make_uint4(a.x, a.y, b.x, b.y);
+    }
+    img[o] = v;
+}
+
+template <int NW, int PRO, int EPI>
+hipError_t go(const F16Params & P, hipStream_t s) {
+    const size_t lds = (size_t) 2 * P.K + NW * 8 + 16;
+    if (lds > 64 * 1024) return hipErrorInvalidValue;
+    LVK_LAUNCH((k_matvec_f16<NW, PRO, EPI>), dim3((P.G + NW - 1) / NW), dim3(NW * 64), lds, s, P);
+    return hipGetLastError();
+}
+
+template <int PRO, int EPI>
+hipError_t go_nw(const F16Params & P, hipStream_t s) {
+    // waves per workgroup: 4 when that still gives every CU two workgroups, else 2 (the
+    // 4096-row matrices: 512 row groups over 256 CUs), so the activation prologue is shared
+    // by as many row groups as the machine's width allows
+    if (P.G >= 8 * cu_count()) return go<4, PRO, EPI>(P, s);
+    return go<2, PRO, EPI>(P, s);
+}
+
+}  // namespace
+
+hipError_t launch_repack_f16(const void * src_rows, int M, int K, uint4 * img, hipStream_t s, int interleave4) {
+    if (K % 256 || M < 1 || (interleave4 && M % 8)) return hipErrorInvalidValue;
+    const size_t n = (size_t) ((M + 7) / 8) * (K / 64) * 64;
+    hipLaunchKernelGGL(k_repack_f16, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, s, (const uint16_t *) src_rows, M,
+                       K, img, interleave4);
+    return hipGetLastError();
+}
+
+hipError_t launch_matvec_f16(const MvLaunch & L, int pro, int epi, hipStream_t s) {
+    if (L.w.qtype != F16 || L.n_tokens != 1) return hipErrorNotSupported;
+    if (L.w.K % 256 || L.w.M < 1) return hipErrorInvalidValue;
+    if (epi != EPI_STORE && L.w.M % 8) return hipErrorInvalidValue;
+    F16Params P{};
+    P.img = L.w.nib;
+    P.M = L.w.M; P.K = L.w.K; P.G = (L.w.M + 7) / 8;
+    P.x = L.x ? L.x + (size_t) L.tok0 * L.w.K : nullptr;
+    P.g = L.g; P.sp = L.sp;
+    P.y = L.y ? L.y + (size_t) L.out_tok0 * L.w.M : nullptr;
+    P.u = L.u;
+    P.q16 = L.q16; P.kc = L.kc; P.vc = L.vc; P.rope = L.rope.cs;
+    P.n_embd = L.n_embd; P.head_dim = L.head_dim; P.n_ctx = L.n_ctx; P.kv32 = L.kv32;
+    P.silu_tab = L.silu_tab;
+    if (!P.x || (pro == PRO_NORM && !P.g)) return hipErrorInvalidValue;
+    if (pro == PRO_NORM) {
+        switch (epi) {
+            case EPI_STORE: return go_nw<PRO_NORM, EPI_STORE>(P, s);
+            case EPI_QKV: return go_nw<PRO_NORM, EPI_QKV>(P, s);
+            case EPI_SWIGLU_F32: return go_nw<PRO_NORM, EPI_SWIGLU_F32>(P, s);
+        }
+    } else if (pro == PRO_ACTF) {
+        switch (epi) {
+            case EPI_STORE: return go_nw<PRO_ACTF, EPI_STORE>(P, s);
+            case EPI_RESID: return go_nw<PRO_ACTF, EPI_RESID>(P, s);
+        }
+    }
+    return hipErrorNotSupported;
+}
+
+}  // namespace lvk

@@ -115,9 +115,16 @@ void Context::init(const llama_context_params & p) {
     u_ffn = (float *) model.alloc(F * 4);
     {
         const size_t Cp = (C + 63) / 64 * 64, KX = std::max(E, F);
-        xh = (uint16_t *) model.alloc(mm_act_bytes((int) Cp, (int) KX));
-        LVK_HIP(hipMemset(xh, 0, mm_act_bytes((int) Cp, (int) KX)));   // masked slots stay zero
-        xda = (float *) model.alloc(Cp * (KX / 32) * 4);
+        if (model.qtype == F16) {
+            // the Q4 operand images are not needed: f16 activation rows and the f32 Wo input
+            x16 = model.alloc(mm_f16_act_bytes((int) C, (int) KX));
+            LVK_HIP(hipMemset(x16, 0, mm_f16_act_bytes((int) C, (int) KX)));
+            attn_f32 = (float *) model.alloc(C * E * 4);
+        } else {
+            xh = (uint16_t *) model.alloc(mm_act_bytes((int) Cp, (int) KX));
+            LVK_HIP(hipMemset(xh, 0, mm_act_bytes((int) Cp, (int) KX)));   // masked slots stay zero
+            xda = (float *) model.alloc(Cp * (KX / 32) * 4);
+        }
         if (model.qtype == Q4_1) xside = model.alloc(mm41_act_side_bytes((int) Cp, (int) KX));
         const char * sq = getenv("LVK_MM_SWIGLU_Q");
         if (model.qtype == Q4_0 && (!sq || atoi(sq) != 0)) {
@@ -228,7 +235,92 @@ void Context::collect_profile() {
     ev_used = 0;
 }
 
-static double qbytes(const QMatrix & w) { return (double) w.M * (w.K / 32) * (w.qtype == Q4_0 ? 20 : 24); }
+static double qbytes(const QMatrix & w) {
+    if (w.qtype == F16) return (double) w.M * w.K * 2;
+    return (double) w.M * (w.K / 32) * (w.qtype == Q4_0 ? 20 : 24);
+}
+
+// The forward pass of an f16 model (ggml_compute_forward_mul_mat_f16_f32 where the Q4 path
+// runs mul_mat_q_f32): the same five launches per layer, with the activations converted to
+// f16 (after RMSNorm * g, or plainly for the Wo and W2 inputs, which the attention and the
+// SwiGLU epilogue hand over in f32) instead of quantized.  n == 1: matvec_f16.hip;
+// n > 1: one conversion launch + mm_f16.hip per matrix, RoPE + KV append by launch_rope_kv.
+void Context::enqueue_forward_f16(int n, bool last_only, const int * tok_src, float * logits_out, bool head, bool embed) {
+    const HParams & hp = model.hp;
+    const int E = (int) hp.n_embd, H = (int) hp.n_head, hd = E / H, F = (int) hp.n_ff(), V = (int) hp.n_vocab;
+    const bool seq_ep = seq_epochs;
+    const bool dec_attn = n == 1 && !old_attention && !kv32 && attention_decode_supported(E, H, n_ctx);
+    if (dec_attn && !seq_ep)
+        LVK_HIP(hipMemsetAsync(attn_gran, 0, attention_decode_scratch_bytes(H, n_ctx), stream));
+    if (model.has_embed && embed)
+        timed_launch(K_EMBED, 0, [&] {
+            return launch_embed(model.tok_emb, model.emb_type, E, n == 1 ? &sp_d->pad0 : tok_src, n, x, stream);
+        });
+    auto mm = [&](const QMatrix & w, const float * xin, const float * g, int K, float * y, int ldy, int epi) {
+        EventSplit ev;      // the two kernels are timed as one
+        ev.first();
+        const hipError_t e = launch_act_f16p(xin, g, n, K, x16, stream);
+        if (e != hipSuccess) return e;
+        ev.last();
+        return launch_mm_f16(w, x16, n, y, ldy, epi, silu_tab, stream);
+    };
+    for (size_t il = 0; il < model.layers.size(); ++il) {
+        const Layer & ly = model.layers[il];
+        uint16_t * kcl = kc_layer(il);
+        uint16_t * vcl = vc_layer(il);
+        // the attention kernels also write their quantized output (aq_attn, unused here)
+        AttnLaunch at{q16, kcl, vcl, scores, aq_attn, Q4_0, exp_tab, sp_d, n, E, H, n_ctx};
+        at.out_f32 = attn_f32;
+        at.exp_computed = exp_computed;
+        at.err = err_d;
+        at.kv32 = kv32;
+        at.seq_epochs = seq_ep ? 1 : 0;
+        if (n == 1) {
+            MvLaunch a;
+            a.w = ly.wqkv; a.x = x; a.g = ly.attn_norm; a.sp = sp_d;
+            a.q16 = q16; a.kc = kcl; a.vc = vcl; a.rope.cs = rope;
+            a.n_embd = E; a.head_dim = hd; a.n_ctx = n_ctx; a.kv32 = kv32;
+            timed_launch(K_QKV, qbytes(ly.wqkv), [&] { return launch_matvec_f16(a, PRO_NORM, EPI_QKV, stream); });
+            if (dec_attn)
+                timed_launch(K_ATTN, 0, [&] { return launch_attention_decode(at, attn_gran, (unsigned) il + 1, stream); });
+            else
+                timed_launch(K_ATTN, 0, [&] { return launch_attention(at, stream); });
+            MvLaunch b;
+            b.w = ly.wo; b.x = attn_f32; b.y = x; b.sp = sp_d;
+            timed_launch(K_WO, qbytes(ly.wo), [&] { return launch_matvec_f16(b, PRO_ACTF, EPI_RESID, stream); });
+            MvLaunch c;
+            c.w = ly.w13; c.x = x; c.g = ly.ffn_norm; c.sp = sp_d; c.silu_tab = silu_tab; c.u = u_ffn;
+            timed_launch(K_W13, qbytes(ly.w13), [&] { return launch_matvec_f16(c, PRO_NORM, EPI_SWIGLU_F32, stream); });
+            MvLaunch d;
+            d.w = ly.w2; d.x = u_ffn; d.y = x; d.sp = sp_d;
+            timed_launch(K_W2, qbytes(ly.w2), [&] { return launch_matvec_f16(d, PRO_ACTF, EPI_RESID, stream); });
+        } else {
+            timed_launch(K_QKV, qbytes(ly.wqkv), [&] { return mm(ly.wqkv, x, ly.attn_norm, E, qkv32, 3 * E, EPI_STORE); });
+            timed_launch(K_QKV, 0, [&] {
+                return launch_rope_kv(qkv32, n, E, hd, rope, sp_d, n_ctx, q16, kcl, vcl, stream, kv32);
+            });
+            if (!kv32 && attention_prompt_supported(E, H, n_ctx))
+                timed_launch(K_ATTN, 0, [&] { return launch_attention_prompt(at, (uint16_t *) scores, nullptr, nullptr, stream); });
+            else
+                timed_launch(K_ATTN, 0, [&] { return launch_attention(at, stream); });
+            timed_launch(K_WO, qbytes(ly.wo), [&] { return mm(ly.wo, attn_f32, nullptr, E, x, E, EPI_RESID); });
+            timed_launch(K_W13, qbytes(ly.w13), [&] { return mm(ly.w13, x, ly.ffn_norm, E, uf, F, EPI_SWIGLU_F32); });
+            timed_launch(K_W2, qbytes(ly.w2), [&] { return mm(ly.w2, uf, nullptr, F, x, E, EPI_RESID); });
+        }
+    }
+    if (!model.has_head || !head) return;   // not the last pipeline stage: x is the output
+    if (last_only || n == 1) {
+        MvLaunch o;
+        o.w = model.output; o.x = x; o.g = model.norm; o.sp = sp_d; o.y = logits_out;
+        o.tok0 = n - 1;
+        timed_launch(K_LMHEAD, qbytes(model.output), [&] { return launch_matvec_f16(o, PRO_NORM, EPI_STORE, stream); });
+    } else {
+        // logits_all: lm_head over every row
+        timed_launch(K_LMHEAD, qbytes(model.output), [&] { return mm(model.output, x, model.norm, E, logits_out, V, EPI_STORE); });
+    }
+    if (want_embedding)
+        LVK_HIP(launch_rmsnorm_rows(x + (size_t) (n - 1) * E, model.norm, E, 1, emb_d, stream));
+}
 
 // decode kernels: the CU-balanced path (matvec_cu.hip) where its row length is
 // compiled in, else the generic kernel
@@ -256,6 +348,10 @@ void Context::enqueue_forward(int n, bool last_only, const int * tok_src, int lo
     if (!tok_src) tok_src = tok_d;
     float * const logits_out = logits_d + (size_t) logit_row * hp.n_vocab;
     const int E = (int) hp.n_embd, H = (int) hp.n_head, hd = E / H, F = (int) hp.n_ff();
+    if (model.qtype == F16) {
+        enqueue_forward_f16(n, last_only, tok_src, logits_out, head, embed);
+        return;
+    }
     if (use_mfma(n)) {
         // prompt batch on the matrix cores: per layer
         //   act(norm) -> QKV (store) -> RoPE + KV append -> attention -> act -> Wo (+x)

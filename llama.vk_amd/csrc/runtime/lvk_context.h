@@ -111,6 +111,11 @@ struct Context {
     // prompt: RoPE + KV append fused into the QKV matmul (LVK_MM_ROPE=0: separate kernel)
     bool mm_rope_fused = [] { const char * e = getenv("LVK_MM_ROPE"); return !e || atoi(e) != 0; }();
     float * uf = nullptr;        // [C][F] silu(w1 x) * (w3 x)
+    // f16 models (model.qtype == F16): the attention's f32 output (the Wo input, converted
+    // to f16 by the matmul's prologue) and the prompt matmuls' f16 activation rows
+    float * attn_f32 = nullptr;  // [C][E]
+    void * x16 = nullptr;        // mm_f16_act_bytes(C, max(E, F))
+    void enqueue_forward_f16(int n, bool last_only, const int * tok_src, float * logits_out, bool head, bool embed);
 
     // decode graph (N = 1, last-token logits)
     hipGraph_t graph = nullptr;

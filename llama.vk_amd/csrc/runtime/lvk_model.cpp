@@ -12,6 +12,8 @@
 // matrices assembled there: wq|wk|wv rows, and w1/w3 interleaved per 32-row
 // block) and repacked on the GPU into the octet image the matvec
 // streams (lvk_kernels.h QMatrix).  The image has exactly the file's bytes.
+// f16 models (every 2-D tensor type 1) take the same route: the staged rows are repacked
+// into the paired-step octet image (f16_common.h), 2 B per weight and no second copy.
 #include "lvk_model.h"
 
 #include <fcntl.h>
@@ -243,8 +245,11 @@ void load_model(Model & m, const std::string & path, bool vocab_only, hipStream_
     Tensor t_tok = get("tok_embeddings.weight", {E, V});
     Tensor t_norm = get("norm.weight", {E});
     Tensor t_out = get("output.weight", {E, V});
-    if (t_out.type != 2 && t_out.type != 3) throw Error("llama.vk_amd: output.weight must be Q4_0/Q4_1");
+    if (t_out.type != 1 && t_out.type != 2 && t_out.type != 3)
+        throw Error("llama.vk_amd: output.weight must be f16, Q4_0 or Q4_1");
     m.qtype = (int) t_out.type;
+    if (m.qtype == F16 && t_tok.type != 1)
+        throw Error("llama.vk_amd: tok_embeddings.weight of an f16 model must be f16 (mixed files are not supported)");
     const size_t rb_E = type_row_bytes(m.qtype, E), rb_F = type_row_bytes(m.qtype, F);
     size_t stage_n = std::max({t_out.size, 3 * E * rb_E, 2 * (size_t) F * rb_E, (size_t) E * rb_F});
     void * stage = nullptr;
@@ -269,6 +274,11 @@ void load_model(Model & m, const std::string & path, bool vocab_only, hipStream_
     auto make_matrix = [&](int M, int K) -> QMatrix {
         QMatrix q;
         q.qtype = m.qtype; q.M = M; q.K = K;
+        if (m.qtype == F16) {
+            q.nib = (const uint4 *) m.alloc(f16_image_bytes(M, K));
+            m.weight_bytes += (size_t) M * K * 2;
+            return q;
+        }
         const size_t nib = qimage_nib_bytes(M, K);
         const size_t scl = qimage_scl_bytes(M, K, m.qtype);
         q.nib = (const uint4 *) m.alloc(nib);
@@ -276,7 +286,8 @@ void load_model(Model & m, const std::string & path, bool vocab_only, hipStream_
         m.weight_bytes += (size_t) M * (K / 32) * (m.qtype == Q4_0 ? 20 : 24);
         return q;
     };
-    // the prompt matmul's f16 A-fragment images (mm_mfma.hip, 2 B per weight: 13.2 GB for
+    // Q4 models only (an f16 model's prompt matmul, mm_f16.hip, streams the decode image): the
+    // prompt matmul's f16 A-fragment images (mm_mfma.hip, 2 B per weight: 13.2 GB for
     // 7B, 130 GB for 65B), decided by capacity (the A-image table):
     //   * Q4_1: the f16 image plus the per-block side image (mm_mfma41.hip, 3 B per weight in
     //     all) are what the Q4_1 MFMA prompt path runs on -- 13B 512-token prompt 158 ms with
@@ -287,7 +298,7 @@ void load_model(Model & m, const std::string & path, bool vocab_only, hipStream_
     //     most a quarter of the device's memory: 7B / 13B-shaped models and every stage of a
     //     65B split over 8 GPUs, not the whole 65B on one GPU (130 GB of 288 GB);
     //     LVK_PROMPT_A16=1 builds it whenever it fits, =0 never
-    bool a16 = prompt_a16_env();
+    bool a16 = m.qtype != F16 && prompt_a16_env();
     if (a16) {
         const size_t EE = (size_t) E * E, EF = (size_t) E * F;
         const size_t per_w = m.qtype == Q4_0 ? 2 : 3;
@@ -299,6 +310,11 @@ void load_model(Model & m, const std::string & path, bool vocab_only, hipStream_
         if (a16 && m.qtype == Q4_0 && !prompt_a16_forced()) a16 = need <= total_b / 4;
     }
     auto repack = [&](QMatrix & q, int interleave4 = 0) {
+        if (q.qtype == F16) {
+            LVK_HIP(launch_repack_f16(stage, q.M, q.K, (uint4 *) q.nib, s, interleave4));
+            LVK_HIP(hipStreamSynchronize(s));
+            return;
+        }
         LVK_HIP(launch_repack(stage, q.qtype, q.M, q.K, (uint4 *) q.nib, (void *) q.scl, s, interleave4));
         if (a16 && q.qtype == Q4_0 && mm_mfma_supported(q)) {
             q.a16 = m.alloc(mm_a16_bytes(q.M, q.K));
@@ -313,7 +329,8 @@ void load_model(Model & m, const std::string & path, bool vocab_only, hipStream_
         LVK_HIP(hipStreamSynchronize(s));
     };
     auto check_q = [&](const Tensor & t, const std::string & name) {
-        if ((int) t.type != m.qtype) throw Error("llama.vk_amd: tensor '" + name + "' is not in the model's Q4 format");
+        if ((int) t.type != m.qtype)
+            throw Error("llama.vk_amd: tensor '" + name + "' is not in the model's weight format (mixed f16 / Q4 files are not supported)");
     };
 
     // embeddings stay in file layout (gathered by row, ggml.c:6868-6895)

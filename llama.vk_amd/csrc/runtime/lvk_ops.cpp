@@ -179,6 +179,36 @@ int lvk_mul_mat_q_mfma(int type, const void * w, int m, int k, const float * g, 
     } catch (const lvk::Error & e) { return fail(__func__, e.msg); }
 }
 
+int lvk_mul_mat_f16(const uint16_t * w, int m, int k, const float * g, const float * x, int n, float * y, int kernel) {
+    try {
+        if (!w || !x || !y || m < 1 || n < 1 || k < 256 || k % 256) return fail(__func__, "need m >= 1, n >= 1, k % 256 == 0");
+        if (kernel < 0 || kernel > 2 || (kernel == 1 && n != 1)) return fail(__func__, "kernel: 0 auto, 1 decode matvec (n == 1), 2 batched");
+        if (kernel == 0) kernel = n == 1 ? 1 : 2;
+        Dev dv;
+        const uint16_t * wd = dv.up(w, (size_t) m * k);
+        lvk::QMatrix q;
+        q.qtype = lvk::F16; q.M = m; q.K = k;
+        q.nib = (const uint4 *) dv.get(lvk::f16_image_bytes(m, k));
+        LVK_HIP(lvk::launch_repack_f16(wd, m, k, (uint4 *) q.nib, nullptr));
+        float * xd = dv.up(x, (size_t) n * k);
+        const float * gd = g ? dv.up(g, (size_t) k) : nullptr;
+        float * yd = (float *) dv.get((size_t) n * m * 4);
+        if (kernel == 1) {
+            lvk::StepParams sp{0, 1, 0, 0};
+            lvk::MvLaunch L;
+            L.w = q; L.x = xd; L.g = gd; L.sp = dv.up(&sp, 1); L.y = yd;
+            LVK_HIP(lvk::launch_matvec_f16(L, g ? lvk::PRO_NORM : lvk::PRO_ACTF, lvk::EPI_STORE, nullptr));
+        } else {
+            void * x16 = dv.get(lvk::mm_f16_act_bytes(n, k));
+            LVK_HIP(hipMemset(x16, 0, lvk::mm_f16_act_bytes(n, k)));
+            LVK_HIP(lvk::launch_act_f16p(xd, gd, n, k, x16, nullptr));
+            LVK_HIP(lvk::launch_mm_f16(q, x16, n, yd, m, lvk::EPI_STORE, nullptr, nullptr));
+        }
+        LVK_HIP(hipMemcpy(y, yd, (size_t) n * m * 4, hipMemcpyDeviceToHost));
+        return 0;
+    } catch (const lvk::Error & e) { return fail(__func__, e.msg); }
+}
+
 int lvk_attention_scores(const uint16_t * kc, const uint16_t * vc, const float * q, int n_embd, int n_head,
                          int n_ctx, int n_past, int n, float * out, float * scores_out);
 int lvk_attention(const uint16_t * kc, const uint16_t * vc, const float * q, int n_embd, int n_head, int n_ctx,

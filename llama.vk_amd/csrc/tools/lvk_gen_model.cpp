@@ -1,4 +1,4 @@
-// lvk-gen-model: seeded synthetic LLaMA model writer (ggjt v1, Q4_0 / Q4_1).
+// lvk-gen-model: seeded synthetic LLaMA model writer (ggjt v1, f16 / Q4_0 / Q4_1).
 //
 // There are no real checkpoints anywhere in this environment, so every parity
 // and performance input is a synthetic ggjt v1 file with the tensor names,
@@ -11,11 +11,15 @@
 //   weights : block scale d = (0.5 + U) * s, s = 1/sqrt(K)/4.6
 //             (tok_embeddings use s = 0.02/4.6), qs = uniform random bytes,
 //             Q4_1 blocks add m = -8*d
+//   f16     : (--ftype 1) element = f16((16 U1 - 8) * (0.5 + U2) * s), the same per-tensor
+//             scale s, so the values spread like the Q4 ones but carry full random 10-bit
+//             mantissas; one element in 256 is a special: +0, -0 or an f16 subnormal with
+//             random mantissa and sign.  1-D tensors stay f32.
 //   norms   : 1 + 0.1 * N(0,1)   (Irwin-Hall approximation of N(0,1))
 //   vocab   : copied from a ggjt vocab section file, or synthetic tokens.
 //
 // usage: lvk-gen-model OUT --n-embd 4096 --n-head 32 --n-layer 32
-//                      [--n-mult 256] [--n-vocab 32000] [--ftype 2|3]
+//                      [--n-mult 256] [--n-vocab 32000] [--ftype 1|2|3]
 //                      [--seed 1] [--vocab tests/golden/vocab32000.bin]
 #include <cmath>
 #include <cstdint>
@@ -74,12 +78,57 @@ void fill_q4(uint8_t * out, uint64_t nblocks, int ftype, float s, const Gen & g,
     for (auto & t : th) t.join();
 }
 
+// f32 -> f16, round to nearest even (finite inputs)
+uint16_t to_f16(float f) {
+    uint32_t x;
+    std::memcpy(&x, &f, 4);
+    const uint32_t sign = (x >> 16) & 0x8000u;
+    x &= 0x7fffffffu;
+    if (x >= 0x47800000u) return (uint16_t) (sign | 0x7c00u);
+    if (x < 0x38800000u) {                       // below the smallest normal f16
+        if (x < 0x33000000u) return (uint16_t) sign;
+        const uint32_t m = (x & 0x7fffffu) | 0x800000u;
+        const int shift = 126 - (int) (x >> 23);
+        uint32_t r = m >> shift;
+        const uint32_t rem = m & ((1u << shift) - 1), half = 1u << (shift - 1);
+        if (rem > half || (rem == half && (r & 1))) ++r;
+        return (uint16_t) (sign | r);
+    }
+    uint32_t r = (x - 0x38000000u) >> 13;
+    const uint32_t rem = x & 0x1fffu;
+    if (rem > 0x1000u || (rem == 0x1000u && (r & 1))) ++r;
+    return (uint16_t) (sign | r);
+}
+
+// fill `out` with `n` f16 elements of a tensor; parallel over elements
+void fill_f16(uint16_t * out, uint64_t n, float s, const Gen & g, uint32_t ti) {
+    unsigned nt = std::max(1u, std::thread::hardware_concurrency());
+    if (nt > 64) nt = 64;
+    std::vector<std::thread> th;
+    for (unsigned w = 0; w < nt; ++w) {
+        th.emplace_back([=, &g] {
+            const uint64_t i0 = n * w / nt, i1 = n * (w + 1) / nt;
+            for (uint64_t i = i0; i < i1; ++i) {
+                const uint64_t h = g.key(ti, i);
+                const uint32_t sel = (uint32_t) h & 1023u;
+                uint16_t v;
+                if (sel == 0) v = 0x0000;
+                else if (sel == 1) v = 0x8000;
+                else if (sel < 4) v = (uint16_t) (((h >> 10) & 0x3ffu) | (((h >> 20) & 1u) << 15));   // subnormal
+                else v = to_f16((unit(h) * 16.0f - 8.0f) * (0.5f + unit(h << 24)) * s);
+                out[i] = v;
+            }
+        });
+    }
+    for (auto & t : th) t.join();
+}
+
 }  // namespace
 
 int main(int argc, char ** argv) {
     if (argc < 2) {
         std::fprintf(stderr, "usage: %s OUT [--n-embd N] [--n-head N] [--n-layer N] [--n-mult N] "
-                             "[--n-vocab N] [--ftype 2|3] [--seed S] [--vocab FILE]\n", argv[0]);
+                             "[--n-vocab N] [--ftype 1|2|3] [--seed S] [--vocab FILE]\n", argv[0]);
         return 2;
     }
     std::string out = argv[1], vocab_path;
@@ -98,7 +147,7 @@ int main(int argc, char ** argv) {
         else if (k == "--vocab") vocab_path = v;
         else { std::fprintf(stderr, "unknown option %s\n", k.c_str()); return 2; }
     }
-    if ((ftype != 2 && ftype != 3) || n_embd % 32 || n_head == 0 || n_embd % n_head) {
+    if ((ftype != 1 && ftype != 2 && ftype != 3) || n_embd % 32 || n_head == 0 || n_embd % n_head) {
         std::fprintf(stderr, "bad hparams\n");
         return 2;
     }
@@ -162,7 +211,11 @@ int main(int argc, char ** argv) {
         th.resize(th.size() + ((32 - (p2 & 31)) & 31), 0);   // llama.cpp:397-400
         std::fwrite(th.data(), 1, th.size(), f);
         pos += th.size();
-        if (is2d) {
+        if (is2d && ftype == 1) {
+            const uint64_t n = (uint64_t) ne0 * ne1;
+            data.resize(2 * n);
+            fill_f16((uint16_t *) data.data(), n, s, g, ti);
+        } else if (is2d) {
             const uint64_t nb = (uint64_t) ne0 / 32 * ne1;
             data.resize(nb * (ftype == 2 ? 20 : 24));
             fill_q4(data.data(), nb, (int) ftype, s, g, ti);

@@ -96,6 +96,7 @@ _sig("lvk_quantize_rows", C.c_int, [C.c_int, f32p, C.c_int, C.c_int, u8p])
 _sig("lvk_mul_mat_q", C.c_int, [C.c_int, u8p, C.c_int, C.c_int, f32p, C.c_int, f32p])
 _sig("lvk_mul_mat_q_norm", C.c_int, [C.c_int, u8p, C.c_int, C.c_int, f32p, f32p, C.c_int, f32p])
 _sig("lvk_mul_mat_q_mfma", C.c_int, [C.c_int, u8p, C.c_int, C.c_int, C.c_void_p, f32p, C.c_int, f32p])
+_sig("lvk_mul_mat_f16", C.c_int, [u16p, C.c_int, C.c_int, C.c_void_p, f32p, C.c_int, f32p, C.c_int])
 _sig("lvk_attention", C.c_int, [u16p, u16p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p])
 _sig("lvk_attention_prompt", C.c_int, [u16p, u16p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p])
 _sig("lvk_attention_decode", C.c_int, [u16p, u16p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, f32p])
@@ -415,6 +416,25 @@ def mul_mat_q_mfma(qtype, w_rows, m, k, x, g=None):
         gp = g.ctypes.data_as(C.c_void_p)
     _check(lib.lvk_mul_mat_q_mfma(qtype, np.ascontiguousarray(w_rows, np.uint8).ravel(), m, k, gp, x, n, y),
            "lvk_mul_mat_q_mfma")
+    return y.reshape(n, m)
+
+
+def mul_mat_f16(w16, x, g=None, kernel=0):
+    """f16 weights w16 [m][k] (uint16 bits or float16) times f32 rows x [n][k] (lvk_mul_mat_f16); g: optional
+    RMSNorm weight; kernel: 0 as a context chooses, 1 the decode matvec (n == 1), 2 the batched matmul"""
+    w16 = np.ascontiguousarray(w16)
+    if w16.dtype == np.float16:
+        w16 = w16.view(np.uint16)
+    w16 = np.ascontiguousarray(w16, np.uint16)
+    m, k = w16.shape
+    x = np.ascontiguousarray(x, np.float32).reshape(-1, k)
+    n = x.shape[0]
+    y = np.zeros(n * m, np.float32)
+    gp = None
+    if g is not None:
+        g = np.ascontiguousarray(g, np.float32)
+        gp = g.ctypes.data_as(C.c_void_p)
+    _check(lib.lvk_mul_mat_f16(w16.ravel(), m, k, gp, x.ravel(), n, y, kernel), "lvk_mul_mat_f16")
     return y.reshape(n, m)
 
 
