@@ -353,10 +353,7 @@ __global__ __launch_bounds__(256) void k_attn_p_pv(const uint16_t * __restrict__
 #pragma unroll
             for (int k = 0; k < 8; ++k)
                 hh[k] = __builtin_bit_cast(uint16_t, (_Float16) (float) ((int) ((word >> (4 * k)) & 15u) - 8));
-            xm[xm_slot(tok, nb, blk, e, tok & 15)] = make_uint2(hh[0] | (uint32_t) hh[2] << 16, hh[1] | (uint32_t) hh[3] << 16);
-            xm[xm_slot(tok, nb, blk, e, 48 + (tok & 15))] =
-                make_uint2(hh[4] | (uint32_t) hh[6] << 16, hh[5] | (uint32_t) hh[7] << 16);
-            if (e == 0) xda[(size_t) tok * nb + blk] = dd;
+            act40_emit(tok, nb, blk, e, hh, dd, xm, xda);
         }
     }
 }
@@ -367,11 +364,14 @@ bool attention_prompt_supported(int n_embd, int n_head, int n_ctx) {
     return n_embd / n_head == HD && n_ctx % 32 == 0 && n_ctx <= 1024;
 }
 
-hipError_t launch_attention_prompt(const AttnLaunch & A, uint16_t * p_scratch, void * xm, float * xda,
-                                   hipStream_t s, void * xs41) {
+hipError_t launch_attention_prompt(const AttnLaunch & A, uint16_t * p_scratch, const ActImage & wo_image,
+                                   hipStream_t s) {
     if (!attention_prompt_supported(A.n_embd, A.n_head, A.n_ctx)) return hipErrorNotSupported;
-    // Q4_1 writes its MFMA operands (xm + xs41) or nothing but the ActQ; Q4_0 xm + xda
-    if (A.out_qtype == Q4_1 ? (xm != nullptr) != (xs41 != nullptr) : A.out_qtype != Q4_0 || xs41)
+    // Q4_1 writes its MFMA operands (xm + xs) or nothing but the ActQ; Q4_0 xm + da
+    void * const xm = wo_image.xm;
+    float * const xda = wo_image.da;
+    void * const xs41 = wo_image.xs;
+    if (A.out_qtype == Q4_1 ? (xm != nullptr) != (xs41 != nullptr) || xda : A.out_qtype != Q4_0 || xs41 || (xm != nullptr) != (xda != nullptr))
         return hipErrorNotSupported;
     const float scale = 1.0f / sqrtf((float) A.n_embd / (float) A.n_head);   // llama.cpp:1028
     constexpr int T = 16;

@@ -179,6 +179,34 @@ __device__ __forceinline__ float rms_mean_wave(double tree, const float * x, int
     LVK_RMS_COUNT(2);
     return rms_mean_in_order(x, n);
 }
+// The RMSNorm scale 1 / sqrt(mean(x^2) + 1e-6) of the row xr[0 .. K) for the batched matmuls'
+// activation quantizers (one 256-thread workgroup per token; call it from uniform control
+// flow, it holds two barriers): the double sum of the float squares per thread over strided
+// 8-element units, a wave tree, the four waves in order, then rms_mean_wave in wave 0
+// (ggml.c:6058-6071) -- the same reduction as the matvec prologue (matvec_q4.hip prologue_norm)
+__device__ __forceinline__ float rms_scale_256(const float * xr, int K) {
+    __shared__ double red[4];
+    __shared__ float s_scale;
+    const int tid = threadIdx.x;
+    double acc = 0.0;
+    for (int u = tid; u < K / 8; u += 256) {
+        const float4 a = *(const float4 *) (xr + u * 8), b = *(const float4 *) (xr + u * 8 + 4);
+        const float e[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+#pragma unroll
+        for (int q = 0; q < 8; ++q) { const float sq = e[q] * e[q]; acc += (double) sq; }
+    }
+    acc = warp_sum_d(acc);
+    if ((tid & 63) == 0) red[tid >> 6] = acc;
+    __syncthreads();
+    if (tid < 64) {             // wave 0: rms_mean_wave splits a re-check over its lanes
+        double s = 0.0;
+        for (int wv = 0; wv < 4; ++wv) s += red[wv];
+        const float mean = rms_mean_wave(s, xr, K);
+        if (tid == 0) s_scale = 1.0f / sqrtf(mean + 1e-6f);
+    }
+    __syncthreads();
+    return s_scale;
+}
 // whole-wave double sum through DPP (quad xor 1, xor 2, half-row and row
 // mirrors) and four readlanes; every lane returns the same value, and the
 // association order is fixed: ((row0 + row1) + (row2 + row3)) of 16-lane trees
@@ -234,6 +262,17 @@ __device__ __forceinline__ size_t xm_slot(int t, int nb, int b, int c, int l) {
     return ((((size_t) (t >> 4) * nb + b) * 2 + (c >> 1)) * 64 + l) * 2 + (c & 1);
 }
 
+// The Q4_0 operand writes of group c (elements 8c .. 8c+7) of block b of token t, h[e] the
+// f16 bits of q_e - 8: chain 2c -> fragment lane n = t % 16 (h = jj = 0), chain 2c+1 -> lane
+// 48 + n (h = jj = 1), each in the order e0 e2 e1 e3; the lane of group 0 also stores the
+// block scale d (the Q4_1 counterpart: mm41_common.h act41_emit)
+__device__ __forceinline__ void act40_emit(int t, int nb, int b, int c, const uint16_t (&h)[8], float d,
+                                           uint2 * __restrict__ xm, float * __restrict__ da) {
+    xm[xm_slot(t, nb, b, c, t & 15)] = make_uint2(h[0] | (uint32_t) h[2] << 16, h[1] | (uint32_t) h[3] << 16);
+    xm[xm_slot(t, nb, b, c, 48 + (t & 15))] = make_uint2(h[4] | (uint32_t) h[6] << 16, h[5] | (uint32_t) h[7] << 16);
+    if (c == 0) da[(size_t) t * nb + b] = d;
+}
+
 // token of workgroup i in a one-workgroup-per-token launch of ceil(N/128)*128 workgroups:
 // workgroup i runs on XCD i % 8, and the 16 tokens of token tile tau all go to XCD tau % 8,
 // so the 16-byte pieces they write into the same fragment-image lines (xm_slot) meet in one
@@ -244,19 +283,17 @@ __device__ __forceinline__ int xcd_grouped_token(int i) {
 }
 
 // prompt-matmul tile of workgroup slot L (its XCD-contiguous index, mm_mfma.hip): row tile
-// rt, token tile tt.  Row tiles outer, token tiles inner; supertile: groups of 4 row tiles x
-// every token tile with the token tiles outer, so the 64 workgroups an XCD runs at once share
-// 4 weight tiles and 16 activation tiles in its L2 instead of 2 weight tiles and the whole
-// activation image (7B 512-token prompt 45.3 -> 43.7 ms, profiles/r04_prompt_variants.jsonl);
-// LVK_MM_SUPERTILE = R > 1 sets the group width (A/B)
-__device__ __forceinline__ void mm_tile(int L, int ntt, int nrt, int supertile, int & rt, int & tt) {
+// rt, token tile tt.  Super tiles of R = 4 row tiles x every token tile with the token tiles
+// outer, so the 64 workgroups an XCD runs at once share 4 weight tiles and 16 activation
+// tiles in its L2 instead of 2 weight tiles and the whole activation image (7B 512-token
+// prompt 45.3 -> 43.7 ms, profiles/r04_prompt_variants.jsonl); the row tiles left over after
+// the last whole super tile go row tile outer, token tile inner
+__device__ __forceinline__ void mm_tile(int L, int ntt, int nrt, int & rt, int & tt) {
+    constexpr int R = 4;
     tt = L % ntt;
     rt = L / ntt;
-    const int R = supertile == 1 ? 4 : supertile;     // row tiles per super tile (1: the default 4)
-    if (R > 1) {
-        const int per = R * ntt, sidx = L / per, wi = L % per;
-        if (R * sidx + R - 1 < nrt) { tt = wi / R; rt = R * sidx + wi % R; }
-    }
+    const int per = R * ntt, sidx = L / per, wi = L % per;
+    if (R * sidx + R - 1 < nrt) { tt = wi / R; rt = R * sidx + wi % R; }
 }
 
 // fmaf(f16 half HA of a, f16 half HB of b, c): v_fma_mix converts both f16 operands

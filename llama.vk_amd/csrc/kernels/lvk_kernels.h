@@ -123,12 +123,14 @@ struct MvLaunch {
     float * u = nullptr;                   // EPI_SWIGLU_F32: u in f32 [N][M/2]
 };
 
+// dispatches on L.w.qtype: Q4_0 here (matvec_q4.hip), Q4_1 and F16 forwarded
 hipError_t launch_matvec(const MvLaunch & L, int pro, int epi, hipStream_t s);
-// the same for Q4_1 weights (matvec_q41.hip); launch_matvec forwards here
+// the same for Q4_1 weights (matvec_q41.hip)
 hipError_t launch_matvec_q41(const MvLaunch & L, int pro, int epi, hipStream_t s);
 
 // single-token decode matvec, one workgroup per CU (matvec_cu.hip for Q4_0,
-// matvec_cu41.hip for Q4_1).  Row lengths compiled in: matvec_cu_supported(K, qtype).
+// matvec_cu41.hip for Q4_1; F16 has one single-token kernel, matvec_f16.hip, for every row
+// length).  Row lengths compiled in: matvec_cu_supported(K, qtype).
 // Returns hipErrorNotSupported for anything else (the caller then uses launch_matvec).
 bool matvec_cu_supported(int K, int qtype = Q4_0);
 hipError_t launch_matvec_cu(const MvLaunch & L, int pro, int epi, hipStream_t s);
@@ -162,11 +164,12 @@ struct AttnLaunch {
 hipError_t launch_attention(const AttnLaunch & A, hipStream_t s);
 // prompt batches (N > 1, Q4_0 / Q4_1 output): scores+softmax per (head, 32 tokens) then
 // P.V per (head, 32 tokens, 32 dims) with the Wo quantization fused
-// (attention_prompt.hip).  p_scratch: H*N*n_ctx f16; optional: also write the Wo
-// input as the MFMA operands -- Q4_0 xm/xda (mm_mfma.hip), Q4_1 xm/xs41 (mm_mfma41.hip).
+// (attention_prompt.hip).  p_scratch: H*N*n_ctx f16; wo_image (optional, all of the type's
+// parts or none): also write the Wo input as the batched matmul's operand image.
+struct ActImage;
 bool attention_prompt_supported(int n_embd, int n_head, int n_ctx);
-hipError_t launch_attention_prompt(const AttnLaunch & A, uint16_t * p_scratch, void * xm, float * xda,
-                                   hipStream_t s, void * xs41 = nullptr);
+hipError_t launch_attention_prompt(const AttnLaunch & A, uint16_t * p_scratch, const ActImage & wo_image,
+                                   hipStream_t s);
 // count into bad_d[0] / bad_d[1] the softmax arguments h <= 0 whose exp computed in
 // double / with the device expf differs from exp_tab[h]; 0 means that mode
 // reproduces the host table exactly
@@ -199,18 +202,84 @@ inline const uint4 * q41_wsum(const QMatrix & w) {
     return (const uint4 *) ((const char *) w.scl + (size_t) w.M * ((w.K / 32 + 31) / 32) * 256);
 }
 
-// prompt-eval (N > 1) Q4_0 matmul on the MFMA cores (mm_mfma.hip), bit-exact
-// like launch_matvec: the matrix cores produce the per-chain integer partials,
-// the VALU runs the reference fp32 chains.  Input: the masked B fragment image
-// xm (mm_act_bytes(N, K) bytes, ZEROED once at allocation: only the active
-// slots are ever written) + da [N][K/32], from launch_act_f16 /
-// launch_actq_to_f16.  epi: EPI_STORE, EPI_RESID (y += W x), EPI_SWIGLU_F32
-// (fused W1|W3 image -> u = silu(w1 x) * (w3 x)).
-bool mm_mfma_supported(const QMatrix & w);
-// prompt-matmul tile order: 1 = super tiles of 4 row tiles (default), 0 = row tiles
-// (LVK_MM_SUPERTILE; device/lvk_device.h mm_tile)
-int mm_supertile();
-size_t mm_act_bytes(int N, int K);
+// ---------------------------------------------------------------------------
+// Batched (N > 1) matmul, bit-exact like launch_matvec.  One interface for the three
+// weight types; launch_mm dispatches on w.qtype:
+//   Q4_0 (mm_mfma.hip): the matrix cores produce the per-chain integer partials, the VALU
+//     runs the reference fp32 chains.  Weights: the octet image, or QMatrix::a16 when built.
+//   Q4_1 (mm_mfma41.hip): the matrix cores also produce the cross-term sums and the scale
+//     products.  Weights: QMatrix::a16 + QMatrix::side, both from launch_build_mm41.
+//   F16 (mm_f16.hip): the fp32 chains of matvec_f16.hip, tiled over tokens.
+// The activations reach the kernels as an operand image of the weight type:
+//   xm : Q4_0 / Q4_1 the masked MFMA B-fragment image (lvk_device.h xm_slot);
+//        F16 the paired-step f16 rows, N rounded up to MM_F16_TPAD rows
+//   da : Q4_0 the block scales [N][K/32]
+//   xs : Q4_1 the side image [N/16][K/32][64] x 16 B (mm41_common.h act41_emit)
+// xm must be ZEROED once at allocation: the writers only ever store the active fragment
+// slots (Q4), and the padding rows' products are computed and dropped (F16).
+struct ActImage {
+    void * xm = nullptr;
+    float * da = nullptr;
+    void * xs = nullptr;
+};
+struct ActImageBytes {
+    size_t xm, da, xs;     // 0: the type has no such part
+};
+constexpr int MM_TN = 16;          // tokens per MFMA tile
+constexpr int MM_F16_TPAD = 32;    // the widest token tile of mm_f16.hip
+inline ActImageBytes act_image_bytes(int qtype, int N, int K) {
+    if (qtype == F16) return {(size_t) ((N + MM_F16_TPAD - 1) / MM_F16_TPAD * MM_F16_TPAD) * K * 2, 0, 0};
+    const size_t tiles = (size_t) (N + MM_TN - 1) / MM_TN, nb = (size_t) K / 32;
+    return {tiles * nb * 4 * 64 * 8, qtype == Q4_0 ? (size_t) N * nb * 4 : 0, qtype == Q4_1 ? tiles * nb * 64 * 16 : 0};
+}
+// f32 rows x[N][K] (rms_norm * g when g != nullptr) -> the operand image: quantize_row_q4_0 /
+// quantize_row_q4_1 (AVX2 branches) or f32 -> f16 RNE
+hipError_t launch_act(int qtype, const float * x, const float * g, int N, int K, const ActImage & out, hipStream_t s);
+// pre-quantized blocks (ActQ of the same type) -> the operand image; F16: hipErrorNotSupported
+hipError_t launch_actq_to_image(int qtype, const ActQ & q, int N, int K, const ActImage & out, hipStream_t s);
+
+// EPI_ROPE_KV: RoPE + KV append in the QKV matmul's epilogue (f16 KV cache): the f32 Q|K|V
+// rows never reach memory; q16 / kc / vc get exactly what launch_rope_kv writes
+struct RopeKV {
+    const float2 * rope;       // [n_ctx][hd/2] cos, sin
+    const StepParams * sp;     // n_past
+    int n_ctx, E, hd;
+    uint16_t * q16, * kc, * vc;
+};
+struct MmLaunch {
+    QMatrix w;
+    ActImage x;                            // the N input rows
+    int N = 0;
+    float * y = nullptr;                   // EPI_STORE: [N][ldy];  EPI_RESID: y += W x;  EPI_SWIGLU_F32: u [N][ldy]
+    int ldy = 0;
+    const uint16_t * silu_tab = nullptr;   // EPI_SWIGLU_F32 / EPI_SWIGLU_Q (fused W1|W3 image)
+    const RopeKV * rk = nullptr;           // EPI_ROPE_KV (set for that epilogue only)
+    // EPI_SWIGLU_Q: u = silu(w1 x) * (w3 x) quantized straight into the W2 input's image (of
+    // N x M/2), as launch_act(u, nullptr, ...) would write it
+    ActImage out;
+};
+// which epilogues a type's kernels implement; launch_mm returns hipErrorNotSupported for the others
+inline bool mm_epi_supported(int qtype, int epi) {
+    switch (epi) {
+        case EPI_STORE: case EPI_RESID: case EPI_SWIGLU_F32: return qtype == F16 || qtype == Q4_0 || qtype == Q4_1;
+        case EPI_ROPE_KV: return qtype == Q4_0 || qtype == Q4_1;
+        case EPI_SWIGLU_Q: return qtype == Q4_0;
+    }
+    return false;
+}
+// the matrix's shape and images fit its type's kernels
+bool mm_supported(const QMatrix & w);
+hipError_t launch_mm(const MmLaunch & L, int epi, hipStream_t s);
+// the per-type halves of launch_act / launch_actq_to_image / launch_mm (reached through them)
+hipError_t act_q40(const float * x, const float * g, int N, int K, const ActImage & out, hipStream_t s);
+hipError_t act_q41(const float * x, const float * g, int N, int K, const ActImage & out, hipStream_t s);
+hipError_t act_f16(const float * x, const float * g, int N, int K, const ActImage & out, hipStream_t s);
+hipError_t actq_image_q40(const ActQ & q, int N, int K, const ActImage & out, hipStream_t s);
+hipError_t actq_image_q41(const ActQ & q, int N, int K, const ActImage & out, hipStream_t s);
+hipError_t mm_q40(const MmLaunch & L, int epi, hipStream_t s);
+hipError_t mm_q41(const MmLaunch & L, int epi, hipStream_t s);
+hipError_t mm_f16(const MmLaunch & L, int epi, hipStream_t s);
+
 // the f16 A-fragment image of a Q4_0 matrix (QMatrix::a16): bytes, and its build from the
 // matrix's octet image (M % 32 == 0)
 size_t mm_a16_bytes(int M, int K);
@@ -225,40 +294,9 @@ inline bool prompt_a16_forced() {
     const char * e = getenv("LVK_PROMPT_A16");
     return e && atoi(e) == 1;
 }
-hipError_t launch_mm_mfma(const QMatrix & w, const void * xm, const float * da, int N, float * y, int ldy,
-                          int out_tok0, int epi, const uint16_t * silu_tab, hipStream_t s);
-// x[N][K] (rms_norm * g when g != nullptr) -> quantize_row_q4_0 -> xm, da
-hipError_t launch_act_f16(const float * x, const float * g, int N, int K, void * xm, float * da, hipStream_t s);
-hipError_t launch_actq_to_f16(const ActQ & q, int N, int K, void * xm, float * da, hipStream_t s);
-// the Q4_1 prompt matmul (mm_mfma41.hip), bit-exact like launch_matvec: the matrix
-// cores produce the chain partials, the cross-term sums and the scale products, the
-// VALU runs ggml_vec_dot_q4_1's fp32 chains.  Weights: QMatrix::a16 (mm_a16_bytes, f16
-// q values) + QMatrix::side (mm41_side_bytes), both from launch_build_mm41.  Tokens: the
-// masked fragment image xm (mm_act_bytes, ZEROED once at allocation) + the side image
-// xs (mm41_act_side_bytes), from launch_act41_f16 / launch_actq41_to_f16.
+// the Q4_1 weight images: QMatrix::a16 (mm_a16_bytes, f16 q values) + QMatrix::side
 size_t mm41_side_bytes(int M, int K);
-size_t mm41_act_side_bytes(int N, int K);
 hipError_t launch_build_mm41(const QMatrix & w, void * a16, void * side, hipStream_t s);
-bool mm_mfma41_supported(const QMatrix & w);
-struct RopeKV;
-hipError_t launch_mm_mfma41(const QMatrix & w, const void * xm, const void * xs, int N, float * y, int ldy, int epi,
-                            const uint16_t * silu_tab, hipStream_t s, const RopeKV * rk = nullptr);   // rk: EPI_ROPE_KV
-hipError_t launch_act41_f16(const float * x, const float * g, int N, int K, void * xm, void * xs, hipStream_t s);
-hipError_t launch_actq41_to_f16(const ActQ & q, int N, int K, void * xm, void * xs, hipStream_t s);
-// the prompt QKV matmul with RoPE + KV append in its epilogue (Q4_0, f16 KV cache): the
-// f32 Q|K|V rows never reach memory; q16 / kc / vc get exactly what launch_rope_kv writes
-struct RopeKV {
-    const float2 * rope;       // [n_ctx][hd/2] cos, sin
-    const StepParams * sp;     // n_past
-    int n_ctx, E, hd;
-    uint16_t * q16, * kc, * vc;
-};
-hipError_t launch_mm_qkv_rope(const QMatrix & w, const void * xm, const float * da, int N, const RopeKV & r, hipStream_t s);
-// the prompt W1|W3 matmul (Q4_0) with SwiGLU and the W2 input's quantize_row_q4_0 in its
-// epilogue: writes the masked fragment image xq (mm_act_bytes(N, M/2), zeroed once) + xqda
-// directly, as launch_act_f16(silu(w1 x) * w3 x, nullptr, ...) would
-hipError_t launch_mm_w13_q(const QMatrix & w, const void * xm, const float * da, int N, const uint16_t * silu_tab,
-                           void * xq, float * xqda, hipStream_t s);
 // RoPE + KV append of stored Q|K|V rows qkv [N][3E]
 hipError_t launch_rope_kv(const float * qkv, int N, int E, int hd, const float2 * rope, const StepParams * sp,
                           int n_ctx, uint16_t * q16, uint16_t * kc, uint16_t * vc, hipStream_t s, int kv32 = 0);
@@ -267,16 +305,9 @@ hipError_t launch_rope_kv(const float * qkv, int N, int E, int hd, const float2 
 inline size_t f16_image_bytes(int M, int K) { return (size_t) ((M + 7) / 8 * 8) * K * 2; }
 hipError_t launch_repack_f16(const void * src_rows, int M, int K, uint4 * img, hipStream_t s, int interleave4 = 0);
 // single-token decode matvec (matvec_f16.hip): PRO_NORM (rms_norm * g -> f16) or PRO_ACTF
-// (f32 -> f16) of the f32 row L.x; EPI_STORE, EPI_RESID, EPI_QKV, EPI_SWIGLU_F32
+// (f32 -> f16) of the f32 row L.x; EPI_STORE, EPI_RESID, EPI_QKV, EPI_SWIGLU_F32.
+// launch_matvec and launch_matvec_cu forward here
 hipError_t launch_matvec_f16(const MvLaunch & L, int pro, int epi, hipStream_t s);
-// batched matmul (mm_f16.hip): the activations' paired f16 rows x16 (mm_f16_act_bytes: N
-// rounded up to MM_F16_TPAD rows, any contents in the padding) from launch_act_f16p (g !=
-// nullptr: rms_norm * g first), then y[N][ldy] = / += W x, or u = silu(w1 x) * (w3 x)
-constexpr int MM_F16_TPAD = 32;
-size_t mm_f16_act_bytes(int N, int K);
-hipError_t launch_act_f16p(const float * x, const float * g, int N, int K, void * x16, hipStream_t s);
-hipError_t launch_mm_f16(const QMatrix & w, const void * x16, int N, float * y, int ldy, int epi,
-                         const uint16_t * silu_tab, hipStream_t s);
 
 // operator-level helpers used by the C ABI tests
 hipError_t launch_quantize_act(const float * x, int N, int K, int qtype, ActQ out, hipStream_t s);

@@ -299,4 +299,51 @@ __device__ __forceinline__ void rope_kv_store(const RopeKV & r, const float (&re
     }
 }
 
+// The stores of a prompt-matmul lane's 16 results res (mm_mfma.hip, mm_mfma41.hip; rows and
+// lanes as above, the jj = 0 lanes hold the results): EPI_STORE, EPI_RESID (y += res),
+// EPI_SWIGLU_F32 and EPI_ROPE_KV (cs from rope_kv_cs)
+template <int EPI>
+__device__ __forceinline__ void mm_epi_store(const float (&res)[16], float * y, int ldy, const uint16_t * silu_tab,
+                                             const RopeKV & rk, const float2 (&cs)[4][2], int N, int n, int lane, int w,
+                                             int m0) {
+    const int h = lane >> 5;
+    const int jj = (lane >> 4) & 1;
+    if constexpr (EPI == EPI_SWIGLU_F32) {
+        // W1|W3 image interleaved per 4 rows: h = 0 lanes hold the w1 rows, h = 1 the w3 rows of the
+        // same outputs (llama.cpp:1085-1096)
+        float o[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) o[i] = __shfl_xor(res[i], 32);
+        if (jj == 0 && h == 0 && n < N) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                float uu[4];
+#pragma unroll
+                for (int p = 0; p < 4; ++p) {
+                    const float sl = f16_to_f32(silu_tab[f32_to_f16(res[4 * q + p])]);  // ggml.c:2495
+                    uu[p] = sl * o[4 * q + p];                                          // llama.cpp:1096
+                }
+                const int row = m0 + 32 * w + 8 * q;
+                *(float4 *) (y + (size_t) n * ldy + row / 2) = make_float4(uu[0], uu[1], uu[2], uu[3]);
+            }
+        }
+    } else if constexpr (EPI == EPI_ROPE_KV) {
+        // RoPE + the f16 q / K / V stores (rope_kv_store); a wave's 32 rows lie in one of Q, K, V
+        if (jj == 0 && n < N) rope_kv_store(rk, res, cs, n, h, w, m0);
+    } else {
+        if (jj == 0 && n < N) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                float4 * yp = (float4 *) (y + (size_t) n * ldy + m0 + 32 * w + 8 * q + 4 * h);
+                if constexpr (EPI == EPI_RESID) {
+                    const float4 r = *yp;                 // ggml_add(cur, inpSA) (llama.cpp:1071,1103)
+                    *yp = make_float4(res[4 * q] + r.x, res[4 * q + 1] + r.y, res[4 * q + 2] + r.z, res[4 * q + 3] + r.w);
+                } else {
+                    *yp = make_float4(res[4 * q], res[4 * q + 1], res[4 * q + 2], res[4 * q + 3]);
+                }
+            }
+        }
+    }
+}
+
 }  // namespace lvk

@@ -2,7 +2,7 @@
 // ggml_compute_forward_mul_mat_f16_f32 (AVX2): the chains of matvec_f16.hip (f16_common.h),
 // tiled so that a weight value is loaded once per tile of T tokens.
 //
-// The activations are converted once per launch sequence (launch_act_f16p: optional
+// The activations are converted once per launch sequence (launch_act: optional
 // RMSNorm * g, then f32 -> f16 RNE) into a global buffer of paired-step rows; a wave owns one
 // 8-row group and T tokens, i.e. 4 T independent fp32 chains per lane.  Per 16-byte weight
 // load a lane issues T 16-byte activation loads (the 8 row lanes of a chain slot read the
@@ -101,24 +101,18 @@ hipError_t go_t(const MmParams & P, hipStream_t s) {
 
 }  // namespace
 
-size_t mm_f16_act_bytes(int N, int K) {
-    return (size_t) ((N + MM_F16_TPAD - 1) / MM_F16_TPAD * MM_F16_TPAD) * K * 2;
-}
-
-hipError_t launch_act_f16p(const float * x, const float * g, int N, int K, void * x16, hipStream_t s) {
-    if (K % 256 || N < 1) return hipErrorInvalidValue;
-    if (g) LVK_LAUNCH((k_act_f16p<true>), dim3(N), dim3(256), 0, s, x, g, K, (uint2 *) x16);
-    else LVK_LAUNCH((k_act_f16p<false>), dim3(N), dim3(256), 0, s, x, g, K, (uint2 *) x16);
+hipError_t act_f16(const float * x, const float * g, int N, int K, const ActImage & out, hipStream_t s) {
+    if (g) LVK_LAUNCH((k_act_f16p<true>), dim3(N), dim3(256), 0, s, x, g, K, (uint2 *) out.xm);
+    else LVK_LAUNCH((k_act_f16p<false>), dim3(N), dim3(256), 0, s, x, g, K, (uint2 *) out.xm);
     return hipGetLastError();
 }
 
-hipError_t launch_mm_f16(const QMatrix & w, const void * x16, int N, float * y, int ldy, int epi,
-                         const uint16_t * silu_tab, hipStream_t s) {
-    if (w.qtype != F16) return hipErrorNotSupported;
-    if (w.K % 256 || w.M < 1 || N < 1 || (epi != EPI_STORE && w.M % 8)) return hipErrorInvalidValue;
+hipError_t mm_f16(const MmLaunch & L, int epi, hipStream_t s) {
+    const QMatrix & w = L.w;
+    if (epi != EPI_STORE && w.M % 8) return hipErrorInvalidValue;
     MmParams P{};
     P.img = w.nib; P.M = w.M; P.K = w.K; P.G = (w.M + 7) / 8;
-    P.x16 = (const uint4 *) x16; P.N = N; P.y = y; P.ldy = ldy; P.silu_tab = silu_tab;
+    P.x16 = (const uint4 *) L.x.xm; P.N = L.N; P.y = L.y; P.ldy = L.ldy; P.silu_tab = L.silu_tab;
     switch (epi) {
         case EPI_STORE: return go_t<EPI_STORE>(P, s);
         case EPI_RESID: return go_t<EPI_RESID>(P, s);

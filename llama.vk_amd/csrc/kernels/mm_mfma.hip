@@ -28,10 +28,10 @@
 //   B (activations): Q4_0-quantized tokens as f16 values q-8, written by the
 //     activation quantizer straight into the masked fragment image
 //       xm[token tile][block][c/2][64 lanes][c%2] x 8 B   (lvk_device.h xm_slot)
-//     (lane (h, jj, n): chain 2c+h of token n when h == jj, else zero), so a
-//     wave loads each fragment with one coalesced global_load_dwordx2 -- no
-//     LDS staging and no barrier per K step; 2 blocks are kept in flight (a
-//     ring of 4 pushes the kernel past 256 VGPRs into scratch).
+//     (lane (h, jj, n): chain 2c+h of token n when h == jj, else zero).  The
+//     token tile's fragments of one sub-chunk (8 blocks x 2 x 64 lanes x 16 B)
+//     are staged once per workgroup in LDS, double-buffered, and every wave
+//     reads its fragments from there (one barrier per sub-chunk).
 //   Scales: dw (octet image) and da staged per 32-block chunk in LDS (one
 //     barrier per chunk); s = dw*da of 32 rows x 16 tokens x 2 blocks comes
 //     from one v_mfma_f32_32x32x1f32 outer product (exact f32 products).
@@ -57,26 +57,7 @@ typedef float f32x32_t __attribute__((ext_vector_type(32)));
 constexpr int TM = 128;     // rows per workgroup
 constexpr int TN = 16;      // tokens per workgroup (one token tile)
 constexpr int NT = 256;     // threads (4 waves)
-// LVK_MM_EXP (dev probe builds only, tools/probe), bit flags: 1 no fp32 chains, 2 no MFMA, 4 no B loads,
-// 64 no B stage global loads (LDS B path), 128 no scale outer-product MFMA, 256 no loop barriers,
-// 8 no A loads, 16 / 32 L2-hot A / B (below)
-#ifndef LVK_MM_EXP
-#define LVK_MM_EXP 0
-#endif
-#ifndef LVK_MM_PD
-#define LVK_MM_PD 2
-#endif
-constexpr int PD = LVK_MM_PD;   // B blocks in flight per wave (ring size divides 8; 4 spills at 256 VGPRs)
-#ifndef LVK_MM_PDA
-#define LVK_MM_PDA 4
-#endif
-// A16 variant: A and B blocks in flight per wave.  4 + 4 measured fastest (7B 512-token
-// prompt 45.4 ms; 4 + 2: 47.7, 2 + 4: 50.7, nibble unpack path 47.3) although it leaves
-// 4-6 VGPRs in scratch at the 256-VGPR budget of two waves per SIMD
-constexpr int PDA = LVK_MM_PDA;
-#ifndef LVK_MM_PDB16
-#define LVK_MM_PDB16 4
-#endif
+constexpr int PDA = 4;      // A16 variant: A blocks in flight per wave
 
 constexpr int DWS = TM + 8;                         // padded row stride of the dw image (conflict-free stores)
 constexpr int DAS = TN + 1;                         // padded stride of the da image
@@ -84,15 +65,9 @@ constexpr int LDS_DW = 32 * DWS * 4;                // [block of chunk][row]
 constexpr int LDS_DA = (32 * DAS * 4 + 15) / 16 * 16;   // [block of chunk][token]
 constexpr int OFF_DW0 = 0, OFF_DW1 = LDS_DW;
 constexpr int OFF_DA0 = 2 * LDS_DW, OFF_DA1 = OFF_DA0 + LDS_DA;
-constexpr int LDS_TOTAL = OFF_DA1 + LDS_DA;         // ~37 KiB
-// A16 + LVK_MM_BLDS: the token tile's B fragments of one sub-chunk (8 blocks x 2 x 64 lanes x
-// 16 B) staged once per workgroup in LDS, double-buffered, instead of each wave loading them
-#ifndef LVK_MM_BLDS
-#define LVK_MM_BLDS 1
-#endif
-constexpr int LDS_BSUB = 8 * 128 * 16;               // 16 KiB per sub-chunk
-constexpr int OFF_B0 = LDS_TOTAL, OFF_B1 = OFF_B0 + LDS_BSUB;
-constexpr int LDS_TOTAL_BL = OFF_B1 + LDS_BSUB;     // ~69 KiB: two workgroups per CU
+constexpr int LDS_BSUB = 8 * 128 * 16;               // the B fragments of one sub-chunk: 16 KiB
+constexpr int OFF_B0 = OFF_DA1 + LDS_DA, OFF_B1 = OFF_B0 + LDS_BSUB;
+constexpr int LDS_TOTAL = OFF_B1 + LDS_BSUB;        // ~69 KiB: two workgroups per CU
 
 struct MmParams {
     const uint4 * nib;
@@ -105,9 +80,7 @@ struct MmParams {
     int ntt;                 // token tiles
     float * y;               // output
     int ldy;
-    int out_tok0;
     const uint16_t * silu_tab;
-    int supertile;           // 1: super tiles of 4 row tiles (default; LVK_MM_SUPERTILE=0: row tiles)
     RopeKV rk;               // EPI_ROPE_KV only
     uint2 * xq;              // EPI_SWIGLU_Q: the W2 input's fragment image, scales, blocks per token
     float * xqda;
@@ -135,14 +108,6 @@ __device__ __forceinline__ half4_t unpack_chain(uint32_t X, uint32_t sel) {
     return r;
 }
 
-__device__ __forceinline__ f32x16_t fake_mfma(half4_t a, half4_t b) {   // LVK_MM_EXP & 2 only
-    f32x16_t r;
-    const float v = (float) a[0] + (float) b[1];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) r[i] = v;
-    return r;
-}
-
 // AVX2 horizontal order (ggml.c:2019-2024) and the epilogue of a wave's 32 rows x 16 tokens:
 // lane (h, n, jj) register set c holds chain 2c+jj; r_j = a_j + a_{j+4} (same lane, sets c and
 // c+2), (r0+r2) | (r1+r3) in lanes jj = 0 | 1, then across the lane pair (xor 16)
@@ -163,26 +128,7 @@ __device__ __forceinline__ void mm_store(const MmParams & P, const f32x16_t (&ac
 
     // ---- epilogue: jj = 0 lanes hold rows 32w + 8q + 4h + p (i = 4q + p) of token n ----
     const int n = n0 + (lane & 15);
-    if constexpr (EPI == EPI_SWIGLU_F32) {
-        // W1|W3 image interleaved per 4 rows: h = 0 lanes hold the w1 rows, h = 1 the w3 rows of the
-        // same outputs (llama.cpp:1085-1096)
-        float o[16];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) o[i] = __shfl_xor(res[i], 32);
-        if (jj == 0 && h == 0 && n < P.N) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                float uu[4];
-#pragma unroll
-                for (int p = 0; p < 4; ++p) {
-                    const float sl = f16_to_f32(P.silu_tab[f32_to_f16(res[4 * q + p])]);  // ggml.c:2495
-                    uu[p] = sl * o[4 * q + p];                                            // llama.cpp:1096
-                }
-                const int row = m0 + 32 * w + 8 * q;
-                *(float4 *) (P.y + (size_t) (P.out_tok0 + n) * P.ldy + row / 2) = make_float4(uu[0], uu[1], uu[2], uu[3]);
-            }
-        }
-    } else if constexpr (EPI == EPI_SWIGLU_Q) {
+    if constexpr (EPI == EPI_SWIGLU_Q) {
         // SwiGLU as EPI_SWIGLU_F32, then quantize_row_q4_0 of the W2 input (ggml.c:621-685, the
         // arithmetic of k_act_q40_f16_tile) straight into its fragment image: the wave's 16
         // outputs (features m0/2 + 16w ..) are half of Q4_0 block b, the other half in wave
@@ -224,22 +170,8 @@ __device__ __forceinline__ void mm_store(const MmParams & P, const f32x16_t (&ac
             }
             if ((w & 1) == 0) P.xqda[(size_t) n * P.nbq + b] = d;
         }
-    } else if constexpr (EPI == EPI_ROPE_KV) {
-        // RoPE + the f16 q / K / V stores (rope_kv_store); a wave's 32 rows lie in one of Q, K, V
-        if (jj == 0 && n < P.N) rope_kv_store(P.rk, res, cs, n, h, w, m0);
     } else {
-        if (jj == 0 && n < P.N) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                float4 * yp = (float4 *) (P.y + (size_t) (P.out_tok0 + n) * P.ldy + m0 + 32 * w + 8 * q + 4 * h);
-                if constexpr (EPI == EPI_RESID) {
-                    const float4 r = *yp;                 // ggml_add(cur, inpSA) (llama.cpp:1071,1103)
-                    *yp = make_float4(res[4 * q] + r.x, res[4 * q + 1] + r.y, res[4 * q + 2] + r.z, res[4 * q + 3] + r.w);
-                } else {
-                    *yp = make_float4(res[4 * q], res[4 * q + 1], res[4 * q + 2], res[4 * q + 3]);
-                }
-            }
-        }
+        mm_epi_store<EPI>(res, P.y, P.ldy, P.silu_tab, P.rk, cs, P.N, n, lane, w, m0);
     }
 }
 
@@ -259,7 +191,7 @@ __global__ __launch_bounds__(NT, 2) void k_mm_q40_mfma(MmParams P) {
     const int full = nwg & ~7;
     const int L = bid < full ? (bid & 7) * (full >> 3) + (bid >> 3) : bid;
     int tt, rt;
-    mm_tile(L, P.ntt, P.M / TM, P.supertile, rt, tt);
+    mm_tile(L, P.ntt, P.M / TM, rt, tt);
     const int m0 = rt * TM;
     const int n0 = tt * TN;
     const int nb = P.nb, NC = P.NC;
@@ -309,40 +241,26 @@ __global__ __launch_bounds__(NT, 2) void k_mm_q40_mfma(MmParams P) {
     auto load_a = [&](int u, uint4 (&A)[4]) {              // sub-chunk u = 8 blocks
         const uint4 * p = ap + (size_t) u * 64;            // (c*4 + sb) * 64 == u * 64
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            if (LVK_MM_EXP & 8) A[c] = make_uint4(u, c, u ^ c, 7);
-            else A[c] = p[2 * c];
-        }
+        for (int c = 0; c < 4; ++c) A[c] = p[2 * c];
     };
     // A16: lane (rho, h) of wave w reads the fragment of rows m0 + 32w + rho, chain 2c + h
-    // LVK_MM_EXP & 16 / 32 (probe builds only): every workgroup reads the weights of row tiles 0..3 /
-    // the activations of token tiles 0..1 (always L2-hot; timing only)
-    const int a_rt = (LVK_MM_EXP & 16) ? (rt & 3) : rt;
-    const uint4 * a16p = A16 ? (const uint4 *) P.a16 + (size_t) (a_rt * TM / 32 + w) * nb * 128 + lane : nullptr;
+    const uint4 * a16p = A16 ? (const uint4 *) P.a16 + (size_t) (rt * TM / 32 + w) * nb * 128 + lane : nullptr;
     uint2 aq[A16 ? PDA : 1][4];
     auto load_aq = [&](int blk, uint2 (&q)[4]) {
 #pragma unroll
         for (int c2 = 0; c2 < 2; ++c2) {
-            const uint4 v = (LVK_MM_EXP & 8) ? make_uint4(blk, c2, 7, 1) : a16p[(size_t) blk * 128 + c2 * 64];
+            const uint4 v = a16p[(size_t) blk * 128 + c2 * 64];
             q[2 * c2] = make_uint2(v.x, v.y);
             q[2 * c2 + 1] = make_uint2(v.z, v.w);
         }
     };
-    // ---- B operand: masked fragments of this token tile, 4 per block ----
-    const uint4 * bp = (const uint4 *) P.xm + (size_t) tt * nb * 128 + lane;   // xm_slot pairs
-    constexpr bool BL = LVK_MM_BLDS;
-    constexpr int PB = BL ? 1 : A16 ? LVK_MM_PDB16 : PD;       // B blocks in flight
-    uint2 bq[PB][4];
-    // BL: sub-chunk u of the token tile is 1024 contiguous uint4; thread tid stages 4 of them
-    const uint4 * bsp = (const uint4 *) P.xm + (size_t) ((LVK_MM_EXP & 32) ? (tt & 1) : tt) * nb * 128 + tid;
+    // ---- B operand: masked fragments of this token tile (xm_slot pairs), 4 per block; sub-chunk
+    // u of the token tile is 1024 contiguous uint4: thread tid stages 4 of them into LDS ----
+    const uint4 * bsp = (const uint4 *) P.xm + (size_t) tt * nb * 128 + tid;
     uint4 bs0, bs1, bs2, bs3;                  // (named: an array of them stays in scratch)
     auto stage_load = [&](int u) {
         const uint4 * g = bsp + (size_t) u * 1024;
-        if (LVK_MM_EXP & 64) {
-            bs0 = make_uint4(u, 1, 2, 3); bs1 = make_uint4(u, 5, 6, 7); bs2 = make_uint4(u, 9, 1, 2); bs3 = make_uint4(u, 3, 4, 5);
-        } else {
-            bs0 = g[0]; bs1 = g[NT]; bs2 = g[2 * NT]; bs3 = g[3 * NT];
-        }
+        bs0 = g[0]; bs1 = g[NT]; bs2 = g[2 * NT]; bs3 = g[3 * NT];
     };
     auto stage_store = [&](int u) {
         uint4 * bl = (uint4 *) (smem + ((u & 1) ? OFF_B1 : OFF_B0)) + tid;
@@ -353,14 +271,6 @@ __global__ __launch_bounds__(NT, 2) void k_mm_q40_mfma(MmParams P) {
 #pragma unroll
         for (int c2 = 0; c2 < 2; ++c2) {
             const uint4 v = bl[c2 * 64];
-            q[2 * c2] = make_uint2(v.x, v.y);
-            q[2 * c2 + 1] = make_uint2(v.z, v.w);
-        }
-    };
-    auto load_bq = [&](int blk, uint2 (&q)[4]) {
-#pragma unroll
-        for (int c2 = 0; c2 < 2; ++c2) {
-            const uint4 v = (LVK_MM_EXP & 4) ? make_uint4(blk, c2, 0, 1) : bp[(size_t) blk * 128 + c2 * 64];
             q[2 * c2] = make_uint2(v.x, v.y);
             q[2 * c2 + 1] = make_uint2(v.z, v.w);
         }
@@ -389,13 +299,8 @@ __global__ __launch_bounds__(NT, 2) void k_mm_q40_mfma(MmParams P) {
     } else {
         load_a(0, Anext);
     }
-    if constexpr (BL) {
-        stage_load(0);
-        stage_store(0);
-    } else {
-#pragma unroll
-        for (int d = 0; d < PB; ++d) load_bq(min(d, nb - 1), bq[d]);
-    }
+    stage_load(0);
+    stage_store(0);
     store_scales(0);
     if constexpr (!A16) make_x(Anext);
     __syncthreads();
@@ -406,7 +311,7 @@ __global__ __launch_bounds__(NT, 2) void k_mm_q40_mfma(MmParams P) {
         const bool scales_next = chunk_last && u + 1 < U;
         if (!A16 && u + 1 < U) load_a(u + 1, Anext);
         if (scales_next) load_scales(ch + 1);
-        if (BL && u + 1 < U) stage_load(u + 1);
+        if (u + 1 < U) stage_load(u + 1);
         const float * wl = (const float *) (smem + ((ch & 1) ? OFF_DW1 : OFF_DW0));
         const float * dl = (const float *) (smem + ((ch & 1) ? OFF_DA1 : OFF_DA0));
         // the block scales s = dw * da (ggml.c:1968) of every (row, token) output come from
@@ -420,18 +325,13 @@ __global__ __launch_bounds__(NT, 2) void k_mm_q40_mfma(MmParams P) {
         for (int jb = 0; jb < 8; ++jb) {
             const int blk = 8 * u + jb;
             const uint32_t sel = (jb & 1) ? 0x0C030C02u : 0x0C010C00u;
-            uint2 (&bf)[4] = bq[jb % PB];
-            if constexpr (BL) lds_bq(u, jb, bf);
+            uint2 bf[4];
+            lds_bq(u, jb, bf);
             if ((jb & 1) == 0) {
                 const int jc = (u & 3) * 8 + jb + h;        // block of the chunk this lane half feeds
                 const float dwa = wl[jc * DWS + 32 * w + rho];
                 const float dab = dl[jc * DAS + (lane & 15)];
-                if (LVK_MM_EXP & 128) {
-#pragma unroll
-                    for (int i = 0; i < 32; ++i) SC[i] = dwa + dab;
-                } else {
-                    SC = __builtin_amdgcn_mfma_f32_32x32x1f32(dwa, dab, (f32x32_t){}, 0, 0, 0);
-                }
+                SC = __builtin_amdgcn_mfma_f32_32x32x1f32(dwa, dab, (f32x32_t){}, 0, 0, 0);
             }
             float sc[16];
 #pragma unroll
@@ -439,36 +339,32 @@ __global__ __launch_bounds__(NT, 2) void k_mm_q40_mfma(MmParams P) {
             // software pipeline: the MFMA of chain pair c+1 is in flight while the VALU runs the
             // chains of pair c (ggml.c:2013: acc_j = fmaf(d, P_j, acc_j))
             f32x16_t Pc[2];
-#define LVK_MFMA(a, b) ((LVK_MM_EXP & 2) ? fake_mfma(a, b) : __builtin_amdgcn_mfma_f32_32x32x8f16(a, b, (f32x16_t){}, 0, 0, 0))
             uint2 (&af)[4] = aq[A16 ? jb % PDA : 0];
             auto afrag = [&](int c) __attribute__((always_inline)) -> half4_t {
                 if constexpr (A16) return __builtin_bit_cast(half4_t, af[c]);
                 else return unpack_chain(X[c][jb >> 1], sel);
             };
-            Pc[0] = LVK_MFMA(afrag(0), __builtin_bit_cast(half4_t, bf[0]));
+            auto mfma = [&](int c) __attribute__((always_inline)) {
+                return __builtin_amdgcn_mfma_f32_32x32x8f16(afrag(c), __builtin_bit_cast(half4_t, bf[c]), (f32x16_t){}, 0, 0, 0);
+            };
+            Pc[0] = mfma(0);
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
-                if (c + 1 < 4)
-                    Pc[(c + 1) & 1] = LVK_MFMA(afrag(c + 1), __builtin_bit_cast(half4_t, bf[c + 1]));
+                if (c + 1 < 4) Pc[(c + 1) & 1] = mfma(c + 1);
 #pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    if (LVK_MM_EXP & 1) acc[c][i] += (i == 0 ? Pc[c & 1][0] + sc[0] : 0.0f);
-                    else acc[c][i] = __builtin_fmaf(sc[i], Pc[c & 1][i], acc[c][i]);
-                }
+                for (int i = 0; i < 16; ++i) acc[c][i] = __builtin_fmaf(sc[i], Pc[c & 1][i], acc[c][i]);
             }
-            // refill this slot with block blk + PD (its MFMAs have read the old fragments)
-            if constexpr (!BL) load_bq(min(blk + PB, nb - 1), bf);
+            // refill this A slot with block blk + PDA (its MFMAs have read the old fragments)
             if constexpr (A16) load_aq(min(blk + PDA, nb - 1), af);
             // block order pinned: unconstrained, hipcc hoists later blocks' MFMAs and spills
 #pragma unroll
             for (int c = 0; c < 4; ++c) asm volatile("" : "+v"(acc[c]));
         }
         if (!A16 && u + 1 < U) make_x(Anext);
-        if (BL && u + 1 < U) stage_store(u + 1);
+        if (u + 1 < U) stage_store(u + 1);
         if (scales_next) store_scales(ch + 1);
-        if ((scales_next || (BL && u + 1 < U)) && !(LVK_MM_EXP & 256))
-            __syncthreads();            // chunk ch+1's scales / sub-chunk u+1's B visible; the buffers of
-                                        // chunk ch-1 / sub-chunk u-1 free again
+        if (u + 1 < U) __syncthreads();   // chunk ch+1's scales / sub-chunk u+1's B visible; the buffers of
+                                          // chunk ch-1 / sub-chunk u-1 free again
     }
 
     mm_store<EPI>(P, acc, lane, w, m0, n0);
@@ -484,34 +380,13 @@ __global__ __launch_bounds__(NT, 2) void k_mm_q40_mfma(MmParams P) {
 template <bool NORM>
 __global__ __launch_bounds__(256) void k_act_q40_f16(const float * __restrict__ x, const float * __restrict__ g,
                                                      int N, int K, uint2 * __restrict__ xm, float * __restrict__ da) {
-    __shared__ double red[4];
-    __shared__ float s_scale;
     const int t = xcd_grouped_token(blockIdx.x);
     if (t >= N) return;
     const int tid = threadIdx.x;
     const int nunits = K / 8;
     const float * xr = x + (size_t) t * K;
     float scale = 1.0f;
-    if constexpr (NORM) {
-        double acc = 0.0;
-        for (int u = tid; u < nunits; u += 256) {
-            const float4 a = *(const float4 *) (xr + u * 8), b = *(const float4 *) (xr + u * 8 + 4);
-            const float e[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-#pragma unroll
-            for (int q = 0; q < 8; ++q) { const float sq = e[q] * e[q]; acc += (double) sq; }
-        }
-        acc = warp_sum_d(acc);
-        if ((tid & 63) == 0) red[tid >> 6] = acc;
-        __syncthreads();
-        if (tid < 64) {             // wave 0: rms_mean_wave splits a re-check over its lanes
-            double s = 0.0;
-            for (int wv = 0; wv < 4; ++wv) s += red[wv];
-            const float mean = rms_mean_wave(s, xr, K);           // ggml.c:6058-6071
-            if (tid == 0) s_scale = 1.0f / sqrtf(mean + 1e-6f);
-        }
-        __syncthreads();
-        scale = s_scale;
-    }
+    if constexpr (NORM) scale = rms_scale_256(xr, K);
     for (int u0 = 0; u0 < nunits; u0 += 256) {
         const int u = u0 + tid;
         const bool live = u < nunits;          // nunits % 4 == 0: quads are all live or all dead
@@ -548,13 +423,7 @@ __global__ __launch_bounds__(256) void k_act_q40_f16(const float * __restrict__ 
                 const int q = ((int) __builtin_rintf(v[e] * id) + 8) & 15;   // ggml.c:655-684
                 h[e] = __builtin_bit_cast(uint16_t, (_Float16) (float) (q - 8));
             }
-            // masked fragment image: chain 2c -> lane n (h = jj = 0), chain 2c+1 -> lane 48 + n (h = jj = 1),
-            // each in the order e0 e2 e1 e3
-            const int nb = K / 32, c = u & 3;
-            xm[xm_slot(t, nb, u >> 2, c, t & 15)] = make_uint2(h[0] | (uint32_t) h[2] << 16, h[1] | (uint32_t) h[3] << 16);
-            xm[xm_slot(t, nb, u >> 2, c, 48 + (t & 15))] =
-                make_uint2(h[4] | (uint32_t) h[6] << 16, h[5] | (uint32_t) h[7] << 16);
-            if ((u & 3) == 0) da[(size_t) t * (K / 32) + (u >> 2)] = d;
+            act40_emit(t, K / 32, u >> 2, u & 3, h, d, xm, da);
         }
     }
 }
@@ -598,9 +467,7 @@ __global__ __launch_bounds__(256) void k_act_q40_f16_tile(const float * __restri
             const int q = ((int) __builtin_rintf(v[e] * id) + 8) & 15;   // ggml.c:655-684
             h[e] = __builtin_bit_cast(uint16_t, (_Float16) (float) (q - 8));
         }
-        xm[xm_slot(t, nb, b, c, tl)] = make_uint2(h[0] | (uint32_t) h[2] << 16, h[1] | (uint32_t) h[3] << 16);
-        xm[xm_slot(t, nb, b, c, 48 + tl)] = make_uint2(h[4] | (uint32_t) h[6] << 16, h[5] | (uint32_t) h[7] << 16);
-        if (c == 0) da[(size_t) t * nb + b] = d;
+        act40_emit(t, nb, b, c, h, d, xm, da);
     }
 }
 
@@ -621,9 +488,7 @@ __global__ void k_actq_to_f16(ActQ q, int N, int K, uint2 * __restrict__ xm, flo
         h[e] = __builtin_bit_cast(uint16_t, (_Float16) (float) (qv - 8));
     }
     const int t = (int) (tb / nb), b = (int) (tb % nb);
-    xm[xm_slot(t, nb, b, c, t & 15)] = make_uint2(h[0] | (uint32_t) h[2] << 16, h[1] | (uint32_t) h[3] << 16);
-    xm[xm_slot(t, nb, b, c, 48 + (t & 15))] = make_uint2(h[4] | (uint32_t) h[6] << 16, h[5] | (uint32_t) h[7] << 16);
-    if (c == 0) da[tb] = q.d[tb];
+    act40_emit(t, nb, b, c, h, c == 0 ? q.d[tb] : 0.0f, xm, da);
 }
 
 // RoPE mode 0 (ggml.c:7156-7227) + KV append (llama.cpp:996-1008) of the
@@ -684,11 +549,6 @@ __global__ void k_a16_from_octet(const uint4 * __restrict__ nib, int M, int K, u
 
 }  // namespace
 
-int mm_supertile() {
-    static const int v = [] { const char * e = getenv("LVK_MM_SUPERTILE"); return e ? atoi(e) : 1; }();
-    return v;
-}
-
 size_t mm_a16_bytes(int M, int K) { return (size_t) (M / 32) * (K / 32) * 256 * 8; }
 
 hipError_t launch_build_a16(const QMatrix & w, void * a16, hipStream_t s) {
@@ -698,89 +558,94 @@ hipError_t launch_build_a16(const QMatrix & w, void * a16, hipStream_t s) {
     return hipGetLastError();
 }
 
-bool mm_mfma_supported(const QMatrix & w) {
-    if (w.qtype == Q4_1) return mm_mfma41_supported(w);
-    return w.qtype == Q4_0 && w.M % TM == 0 && w.K % 256 == 0;
+bool mm_supported(const QMatrix & w) {
+    switch (w.qtype) {
+        case Q4_0: return w.M % TM == 0 && w.K % 256 == 0;
+        case Q4_1: return w.a16 && w.side && w.M % TM == 0 && w.K % 256 == 0;
+        case F16: return w.M >= 1 && w.K % 256 == 0;
+    }
+    return false;
 }
 
-size_t mm_act_bytes(int N, int K) { return (size_t) ((N + TN - 1) / TN) * (K / 32) * 4 * 64 * 8; }
-
-hipError_t launch_mm_mfma(const QMatrix & w, const void * xm, const float * da, int N, float * y, int ldy,
-                          int out_tok0, int epi, const uint16_t * silu_tab, hipStream_t s) {
-    if (w.qtype != Q4_0 || !mm_mfma_supported(w) || N <= 0) return hipErrorInvalidValue;
+hipError_t mm_q40(const MmLaunch & L, int epi, hipStream_t s) {
+    const QMatrix & w = L.w;
     MmParams P{};
+    if (epi == EPI_ROPE_KV) {
+        if (w.M != 3 * L.rk->E || L.rk->E % 32 || L.rk->hd % 4 || !L.rk->sp) return hipErrorInvalidValue;
+        P.rk = *L.rk;
+    }
+    if (epi == EPI_SWIGLU_Q) {
+        if (w.M % 64 || !L.silu_tab || !L.out.xm || !L.out.da) return hipErrorInvalidValue;
+        P.xq = (uint2 *) L.out.xm; P.xqda = L.out.da; P.nbq = w.M / 64;
+    }
     P.nib = w.nib; P.scl = (const float4 *) w.scl;
     P.M = w.M; P.K = w.K; P.nb = w.K / 32; P.NC = (P.nb + 31) / 32;
-    P.xm = (const uint2 *) xm; P.da = da; P.N = N; P.ntt = (N + TN - 1) / TN;
-    P.y = y; P.ldy = ldy; P.out_tok0 = out_tok0; P.silu_tab = silu_tab;
+    P.xm = (const uint2 *) L.x.xm; P.da = L.x.da; P.N = L.N; P.ntt = (L.N + TN - 1) / TN;
+    P.y = L.y; P.ldy = L.ldy; P.silu_tab = L.silu_tab;
     P.a16 = (const uint2 *) w.a16;
-    P.supertile = mm_supertile();
     const dim3 grid((w.M / TM) * P.ntt);
 #define LVK_MM_GO(E)                                                                      \
     do {                                                                                  \
-        if (P.a16) LVK_LAUNCH((k_mm_q40_mfma<E, true>), grid, dim3(NT), LVK_MM_BLDS ? LDS_TOTAL_BL : LDS_TOTAL, s, P); \
-        else LVK_LAUNCH((k_mm_q40_mfma<E, false>), grid, dim3(NT), LVK_MM_BLDS ? LDS_TOTAL_BL : LDS_TOTAL, s, P); \
+        if (P.a16) LVK_LAUNCH((k_mm_q40_mfma<E, true>), grid, dim3(NT), LDS_TOTAL, s, P); \
+        else LVK_LAUNCH((k_mm_q40_mfma<E, false>), grid, dim3(NT), LDS_TOTAL, s, P);      \
     } while (0)
     switch (epi) {
         case EPI_STORE: LVK_MM_GO(EPI_STORE); break;
         case EPI_RESID: LVK_MM_GO(EPI_RESID); break;
         case EPI_SWIGLU_F32: LVK_MM_GO(EPI_SWIGLU_F32); break;
-        default: return hipErrorInvalidValue;
+        case EPI_ROPE_KV: LVK_MM_GO(EPI_ROPE_KV); break;
+        case EPI_SWIGLU_Q: LVK_MM_GO(EPI_SWIGLU_Q); break;
+        default: return hipErrorNotSupported;
     }
 #undef LVK_MM_GO
     return hipGetLastError();
 }
 
-hipError_t launch_mm_qkv_rope(const QMatrix & w, const void * xm, const float * da, int N, const RopeKV & r,
-                              hipStream_t s) {
-    if (w.qtype != Q4_0 || !mm_mfma_supported(w) || N <= 0 || w.M != 3 * r.E || r.E % 32 || r.hd % 4 || !r.sp)
-        return hipErrorInvalidValue;
-    MmParams P{};
-    P.nib = w.nib; P.scl = (const float4 *) w.scl;
-    P.M = w.M; P.K = w.K; P.nb = w.K / 32; P.NC = (P.nb + 31) / 32;
-    P.xm = (const uint2 *) xm; P.da = da; P.N = N; P.ntt = (N + TN - 1) / TN;
-    P.a16 = (const uint2 *) w.a16;
-    P.supertile = mm_supertile();
-    P.rk = r;
-    const dim3 grid((w.M / TM) * P.ntt);
-    if (P.a16) LVK_LAUNCH((k_mm_q40_mfma<EPI_ROPE_KV, true>), grid, dim3(NT), LVK_MM_BLDS ? LDS_TOTAL_BL : LDS_TOTAL, s, P);
-    else LVK_LAUNCH((k_mm_q40_mfma<EPI_ROPE_KV, false>), grid, dim3(NT), LVK_MM_BLDS ? LDS_TOTAL_BL : LDS_TOTAL, s, P);
+hipError_t act_q40(const float * x, const float * g, int N, int K, const ActImage & out, hipStream_t s) {
+    uint2 * xm = (uint2 *) out.xm;
+    if (g)   // one workgroup per token, XCD-grouped token order
+        LVK_LAUNCH(k_act_q40_f16<true>, dim3((unsigned) ((N + 127) / 128 * 128)), dim3(256), 0, s, x, g, N, K, xm, out.da);
+    else
+        LVK_LAUNCH(k_act_q40_f16_tile, dim3((N + 15) / 16, (K / 32 + 3) / 4), dim3(256), 0, s, x, N, K, xm, out.da);
     return hipGetLastError();
 }
 
-hipError_t launch_mm_w13_q(const QMatrix & w, const void * xm, const float * da, int N, const uint16_t * silu_tab,
-                           void * xq, float * xqda, hipStream_t s) {
-    if (w.qtype != Q4_0 || !mm_mfma_supported(w) || N <= 0 || w.M % 64 || !silu_tab || !xq || !xqda)
-        return hipErrorInvalidValue;
-    MmParams P{};
-    P.nib = w.nib; P.scl = (const float4 *) w.scl;
-    P.M = w.M; P.K = w.K; P.nb = w.K / 32; P.NC = (P.nb + 31) / 32;
-    P.xm = (const uint2 *) xm; P.da = da; P.N = N; P.ntt = (N + TN - 1) / TN;
-    P.a16 = (const uint2 *) w.a16;
-    P.supertile = mm_supertile();
-    P.silu_tab = silu_tab;
-    P.xq = (uint2 *) xq; P.xqda = xqda; P.nbq = w.M / 64;
-    const dim3 grid((w.M / TM) * P.ntt);
-    if (P.a16) LVK_LAUNCH((k_mm_q40_mfma<EPI_SWIGLU_Q, true>), grid, dim3(NT), LVK_MM_BLDS ? LDS_TOTAL_BL : LDS_TOTAL, s, P);
-    else LVK_LAUNCH((k_mm_q40_mfma<EPI_SWIGLU_Q, false>), grid, dim3(NT), LVK_MM_BLDS ? LDS_TOTAL_BL : LDS_TOTAL, s, P);
-    return hipGetLastError();
-}
-
-hipError_t launch_act_f16(const float * x, const float * g, int N, int K, void * xm, float * da, hipStream_t s) {
-    if (K % 256 || N <= 0) return hipErrorInvalidValue;
-    static const bool tile = [] { const char * e = getenv("LVK_ACT_TILE"); return !e || atoi(e) != 0; }();
-    const dim3 gt((unsigned) ((N + 127) / 128 * 128));   // k_act_q40_f16: XCD-grouped token order
-    if (g) LVK_LAUNCH(k_act_q40_f16<true>, gt, dim3(256), 0, s, x, g, N, K, (uint2 *) xm, da);
-    else if (tile)
-        LVK_LAUNCH(k_act_q40_f16_tile, dim3((N + 15) / 16, (K / 32 + 3) / 4), dim3(256), 0, s, x, N, K, (uint2 *) xm, da);
-    else LVK_LAUNCH(k_act_q40_f16<false>, gt, dim3(256), 0, s, x, g, N, K, (uint2 *) xm, da);
-    return hipGetLastError();
-}
-
-hipError_t launch_actq_to_f16(const ActQ & q, int N, int K, void * xm, float * da, hipStream_t s) {
+hipError_t actq_image_q40(const ActQ & q, int N, int K, const ActImage & out, hipStream_t s) {
     const long n = (long) N * (K / 32) * 4;
-    LVK_LAUNCH(k_actq_to_f16, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, s, q, N, K, (uint2 *) xm, da);
+    LVK_LAUNCH(k_actq_to_f16, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, s, q, N, K, (uint2 *) out.xm, out.da);
     return hipGetLastError();
+}
+
+// ---- the type dispatch of the batched matmul interface (lvk_kernels.h) ----
+static bool image_complete(int qtype, const ActImage & im) {
+    return im.xm && (qtype != Q4_0 || im.da) && (qtype != Q4_1 || im.xs);
+}
+
+hipError_t launch_act(int qtype, const float * x, const float * g, int N, int K, const ActImage & out, hipStream_t s) {
+    if (K % 256 || N <= 0 || !x || !image_complete(qtype, out)) return hipErrorInvalidValue;
+    switch (qtype) {
+        case Q4_0: return act_q40(x, g, N, K, out, s);
+        case Q4_1: return act_q41(x, g, N, K, out, s);
+        case F16: return act_f16(x, g, N, K, out, s);
+    }
+    return hipErrorNotSupported;
+}
+
+hipError_t launch_actq_to_image(int qtype, const ActQ & q, int N, int K, const ActImage & out, hipStream_t s) {
+    if (qtype != Q4_0 && qtype != Q4_1) return hipErrorNotSupported;
+    if (K % 32 || N <= 0 || !image_complete(qtype, out)) return hipErrorInvalidValue;
+    return qtype == Q4_0 ? actq_image_q40(q, N, K, out, s) : actq_image_q41(q, N, K, out, s);
+}
+
+hipError_t launch_mm(const MmLaunch & L, int epi, hipStream_t s) {
+    if (!mm_epi_supported(L.w.qtype, epi)) return hipErrorNotSupported;
+    if (!mm_supported(L.w) || L.N <= 0 || !image_complete(L.w.qtype, L.x) || (epi == EPI_ROPE_KV) != (L.rk != nullptr))
+        return hipErrorInvalidValue;
+    switch (L.w.qtype) {
+        case Q4_0: return mm_q40(L, epi, s);
+        case Q4_1: return mm_q41(L, epi, s);
+        default: return mm_f16(L, epi, s);
+    }
 }
 
 hipError_t launch_rope_kv(const float * qkv, int N, int E, int hd, const float2 * rope, const StepParams * sp,

@@ -49,10 +49,7 @@ typedef float f32x32_t __attribute__((ext_vector_type(32)));
 constexpr int TM = 128;     // rows per workgroup
 constexpr int TN = 16;      // tokens per workgroup
 constexpr int NT = 256;     // 4 waves
-#ifndef LVK_MM41_PD
-#define LVK_MM41_PD 3
-#endif
-constexpr int PD = LVK_MM41_PD;   // blocks of every operand in flight per wave
+constexpr int PD = 3;       // blocks of every operand in flight per wave
 
 struct Mm41Params {
     const uint4 * a16;       // [M/32][nb][2][64]
@@ -63,7 +60,6 @@ struct Mm41Params {
     float * y;
     int ldy;
     const uint16_t * silu_tab;
-    int supertile;           // mm_tile order (mm_mfma.hip)
     RopeKV rk;               // EPI_ROPE_KV only
 };
 
@@ -76,7 +72,7 @@ template <int EPI>
 __device__ __forceinline__ void epilogue41(const Mm41Params & P, const f32x16_t (&acc)[4], const f32x16_t & off,
                                            int lane, int w, int m0, int n0) {
     // AVX2 horizontal order (ggml.c:2250-2256) as in mm_mfma.hip, then + off * 32 (QK)
-    const int jj = (lane >> 4) & 1, h = lane >> 5;
+    const int h = lane >> 5;
     float2 cs[4][2];                                  // EPI_ROPE_KV: cos / sin (rope_kv_cs)
     if constexpr (EPI == EPI_ROPE_KV) rope_kv_cs(P.rk, P.N, n0 + (lane & 15), h, w, m0, cs);
     float res[16];
@@ -89,39 +85,7 @@ __device__ __forceinline__ void epilogue41(const Mm41Params & P, const f32x16_t 
         res[i] = hs + off[i] * 32.0f;
     }
     const int n = n0 + (lane & 15);
-    if constexpr (EPI == EPI_SWIGLU_F32) {
-        float o[16];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) o[i] = __shfl_xor(res[i], 32);
-        if (jj == 0 && h == 0 && n < P.N) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                float uu[4];
-#pragma unroll
-                for (int p = 0; p < 4; ++p) {
-                    const float sl = f16_to_f32(P.silu_tab[f32_to_f16(res[4 * q + p])]);  // ggml.c:2495
-                    uu[p] = sl * o[4 * q + p];                                            // llama.cpp:1096
-                }
-                const int row = m0 + 32 * w + 8 * q;
-                *(float4 *) (P.y + (size_t) n * P.ldy + row / 2) = make_float4(uu[0], uu[1], uu[2], uu[3]);
-            }
-        }
-    } else if constexpr (EPI == EPI_ROPE_KV) {
-        if (jj == 0 && n < P.N) rope_kv_store(P.rk, res, cs, n, h, w, m0);
-    } else {
-        if (jj == 0 && n < P.N) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                float4 * yp = (float4 *) (P.y + (size_t) n * P.ldy + m0 + 32 * w + 8 * q + 4 * h);
-                if constexpr (EPI == EPI_RESID) {
-                    const float4 r = *yp;
-                    *yp = make_float4(res[4 * q] + r.x, res[4 * q + 1] + r.y, res[4 * q + 2] + r.z, res[4 * q + 3] + r.w);
-                } else {
-                    *yp = make_float4(res[4 * q], res[4 * q + 1], res[4 * q + 2], res[4 * q + 3]);
-                }
-            }
-        }
-    }
+    mm_epi_store<EPI>(res, P.y, P.ldy, P.silu_tab, P.rk, cs, P.N, n, lane, w, m0);
 }
 
 template <int EPI>
@@ -134,7 +98,7 @@ __global__ __launch_bounds__(NT, 2) void k_mm_q41_mfma(Mm41Params P) {
     const int full = nwg & ~7;
     const int L = bid < full ? (bid & 7) * (full >> 3) + (bid >> 3) : bid;
     int tt, rtile;
-    mm_tile(L, P.ntt, P.M / TM, P.supertile, rtile, tt);
+    mm_tile(L, P.ntt, P.M / TM, rtile, tt);
     const int m0 = rtile * TM;
     const int n0 = tt * TN;
     const int nb = P.nb;
@@ -217,17 +181,8 @@ __global__ __launch_bounds__(NT, 2) void k_mm_q41_mfma(Mm41Params P) {
 // side, xm pair halves, xs: one 16-byte lane row each, read back with one ds_read_b128
 // per lane and operand); 72 KiB per workgroup, two workgroups per CU.
 // ---------------------------------------------------------------------------
-#ifndef LVK_MM41_RS
-#define LVK_MM41_RS 3
-#endif
-#ifndef LVK_MM41_OCC
-#define LVK_MM41_OCC 2
-#endif
-constexpr int RS = LVK_MM41_RS;             // ring slots (blocks in flight) per wave
-constexpr int OCC41 = LVK_MM41_OCC;         // workgroups per CU (LDS: OCC41 * LDS41 <= 160 KiB)
-#ifndef LVK_MM41_PIPE
-#define LVK_MM41_PIPE 0
-#endif
+constexpr int RS = 3;                       // ring slots (blocks in flight) per wave
+constexpr int OCC41 = 2;                    // workgroups per CU (LDS: OCC41 * LDS41 <= 160 KiB)
 constexpr int SLOT = 6 * 1024;
 constexpr int LDS41 = 4 * RS * SLOT;
 
@@ -252,7 +207,7 @@ __global__ __launch_bounds__(NT, OCC41) void k_mm_q41_dma(Mm41Params P) {
     const int full = nwg & ~7;
     const int L = bid < full ? (bid & 7) * (full >> 3) + (bid >> 3) : bid;
     int tt, rtile;
-    mm_tile(L, P.ntt, P.M / TM, P.supertile, rtile, tt);
+    mm_tile(L, P.ntt, P.M / TM, rtile, tt);
     const int m0 = rtile * TM;
     const int n0 = tt * TN;
     const int nb = P.nb;
@@ -317,22 +272,6 @@ __global__ __launch_bounds__(NT, OCC41) void k_mm_q41_dma(Mm41Params P) {
             const half4_t bs = __builtin_bit_cast(half4_t, (c < 2) ? make_uint2(ym, 0u) : make_uint2(0u, ym));
             return __builtin_amdgcn_mfma_f32_32x32x8f16(ax, bs, (f32x16_t){}, 0, 0, 0);
         };
-#if LVK_MM41_PIPE
-        // software pipeline: chain pair c+1's MFMAs are issued before chain pair c's FMAs
-        f32x16_t Pn = mfma_p(0), Sn = mfma_s(0);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const f32x16_t Pc = Pn, Sc = Sn;
-            if (c < 3) { Pn = mfma_p(c + 1); Sn = mfma_s(c + 1); }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                acc[c][i] = __builtin_fmaf(SM[i], Pc[i], acc[c][i]);      // ggml.c:2244
-                acc[c][i] = __builtin_fmaf(SX[i], Sc[i], acc[c][i]);      // ggml.c:2247
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-#else
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             const f32x16_t Pc = mfma_p(c);
@@ -343,7 +282,6 @@ __global__ __launch_bounds__(NT, OCC41) void k_mm_q41_dma(Mm41Params P) {
                 acc[c][i] = __builtin_fmaf(SX[i], Sc[i], acc[c][i]);      // ggml.c:2247
             }
         }
-#endif
 #pragma unroll
         for (int i = 0; i < 16; ++i) off[i] = off[i] + SM[16 + i];      // ggml.c:2226
 #pragma unroll
@@ -360,34 +298,13 @@ __global__ __launch_bounds__(NT, OCC41) void k_mm_q41_dma(Mm41Params P) {
 template <bool NORM>
 __global__ __launch_bounds__(256) void k_act_q41_f16(const float * __restrict__ x, const float * __restrict__ g, int N,
                                                      int K, uint4 * __restrict__ xm, uint4 * __restrict__ xs) {
-    __shared__ double red[4];
-    __shared__ float s_scale;
     const int t = xcd_grouped_token(blockIdx.x);
     if (t >= N) return;
     const int tid = threadIdx.x;
     const int nunits = K / 8;
     const float * xr = x + (size_t) t * K;
     float scale = 1.0f;
-    if constexpr (NORM) {
-        double acc = 0.0;
-        for (int u = tid; u < nunits; u += 256) {
-            const float4 a = *(const float4 *) (xr + u * 8), b = *(const float4 *) (xr + u * 8 + 4);
-            const float e[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-#pragma unroll
-            for (int q = 0; q < 8; ++q) { const float sq = e[q] * e[q]; acc += (double) sq; }
-        }
-        acc = warp_sum_d(acc);
-        if ((tid & 63) == 0) red[tid >> 6] = acc;
-        __syncthreads();
-        if (tid < 64) {             // wave 0: rms_mean_wave splits a re-check over its lanes
-            double s = 0.0;
-            for (int wv = 0; wv < 4; ++wv) s += red[wv];
-            const float mean = rms_mean_wave(s, xr, K);           // ggml.c:6058-6071
-            if (tid == 0) s_scale = 1.0f / sqrtf(mean + 1e-6f);
-        }
-        __syncthreads();
-        scale = s_scale;
-    }
+    if constexpr (NORM) scale = rms_scale_256(xr, K);
     for (int u0 = 0; u0 < nunits; u0 += 256) {
         const int u = u0 + tid;
         const bool live = u < nunits;          // nunits % 4 == 0: quads are all live or all dead
@@ -475,7 +392,6 @@ __global__ void k_mm41_images(const uint4 * __restrict__ nibi, const float * __r
 }  // namespace
 
 size_t mm41_side_bytes(int M, int K) { return (size_t) (M / 32) * (K / 32) * 64 * 16; }
-size_t mm41_act_side_bytes(int N, int K) { return (size_t) ((N + TN - 1) / TN) * (K / 32) * 64 * 16; }
 
 hipError_t launch_build_mm41(const QMatrix & w, void * a16, void * side, hipStream_t s) {
     if (w.qtype != Q4_1 || w.M % 32 || w.K % 256) return hipErrorInvalidValue;
@@ -485,23 +401,17 @@ hipError_t launch_build_mm41(const QMatrix & w, void * a16, void * side, hipStre
     return hipGetLastError();
 }
 
-bool mm_mfma41_supported(const QMatrix & w) {
-    return w.qtype == Q4_1 && w.a16 && w.side && w.M % TM == 0 && w.K % 256 == 0;
-}
-
-hipError_t launch_mm_mfma41(const QMatrix & w, const void * xm, const void * xs, int N, float * y, int ldy, int epi,
-                            const uint16_t * silu_tab, hipStream_t s, const RopeKV * rk) {
-    if (!mm_mfma41_supported(w) || N <= 0 || (epi == EPI_ROPE_KV) != (rk != nullptr)) return hipErrorInvalidValue;
+hipError_t mm_q41(const MmLaunch & L, int epi, hipStream_t s) {
+    const QMatrix & w = L.w;
     Mm41Params P{};
-    if (rk) {
-        if (w.M != 3 * rk->E || rk->E % 32 || rk->hd % 4 || !rk->sp) return hipErrorInvalidValue;
-        P.rk = *rk;
+    if (epi == EPI_ROPE_KV) {
+        if (w.M != 3 * L.rk->E || L.rk->E % 32 || L.rk->hd % 4 || !L.rk->sp) return hipErrorInvalidValue;
+        P.rk = *L.rk;
     }
     P.a16 = (const uint4 *) w.a16; P.side = (const uint4 *) w.side;
-    P.xm = (const uint4 *) xm; P.xs = (const uint4 *) xs;
-    P.M = w.M; P.nb = w.K / 32; P.N = N; P.ntt = (N + TN - 1) / TN;
-    P.y = y; P.ldy = ldy; P.silu_tab = silu_tab;
-    P.supertile = mm_supertile();
+    P.xm = (const uint4 *) L.x.xm; P.xs = (const uint4 *) L.x.xs;
+    P.M = w.M; P.nb = w.K / 32; P.N = L.N; P.ntt = (L.N + TN - 1) / TN;
+    P.y = L.y; P.ldy = L.ldy; P.silu_tab = L.silu_tab;
     const dim3 grid((w.M / TM) * P.ntt);
     // LVK_MM41_DMA=0: the register-ring kernel instead of the LDS-DMA ring
     const char * dma_env = getenv("LVK_MM41_DMA");
@@ -516,25 +426,23 @@ hipError_t launch_mm_mfma41(const QMatrix & w, const void * xm, const void * xs,
         case EPI_RESID: LVK_MM41_GO(EPI_RESID); break;
         case EPI_SWIGLU_F32: LVK_MM41_GO(EPI_SWIGLU_F32); break;
         case EPI_ROPE_KV: LVK_MM41_GO(EPI_ROPE_KV); break;
-        default: return hipErrorInvalidValue;
+        default: return hipErrorNotSupported;
     }
 #undef LVK_MM41_GO
     return hipGetLastError();
 }
 
-hipError_t launch_act41_f16(const float * x, const float * g, int N, int K, void * xm, void * xs, hipStream_t s) {
-    if (K % 256 || N <= 0) return hipErrorInvalidValue;
+hipError_t act_q41(const float * x, const float * g, int N, int K, const ActImage & out, hipStream_t s) {
     const dim3 gt((unsigned) ((N + 127) / 128 * 128));   // XCD-grouped token order
-    if (g) LVK_LAUNCH(k_act_q41_f16<true>, gt, dim3(256), 0, s, x, g, N, K, (uint4 *) xm, (uint4 *) xs);
-    else LVK_LAUNCH(k_act_q41_f16<false>, gt, dim3(256), 0, s, x, g, N, K, (uint4 *) xm, (uint4 *) xs);
+    if (g) LVK_LAUNCH(k_act_q41_f16<true>, gt, dim3(256), 0, s, x, g, N, K, (uint4 *) out.xm, (uint4 *) out.xs);
+    else LVK_LAUNCH(k_act_q41_f16<false>, gt, dim3(256), 0, s, x, g, N, K, (uint4 *) out.xm, (uint4 *) out.xs);
     return hipGetLastError();
 }
 
-hipError_t launch_actq41_to_f16(const ActQ & q, int N, int K, void * xm, void * xs, hipStream_t s) {
-    if (K % 32 || N <= 0) return hipErrorInvalidValue;
+hipError_t actq_image_q41(const ActQ & q, int N, int K, const ActImage & out, hipStream_t s) {
     const long n = (long) N * (K / 32) * 4;
-    LVK_LAUNCH(k_actq41_to_f16, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, s, q, N, K, (uint4 *) xm,
-               (uint4 *) xs);
+    LVK_LAUNCH(k_actq41_to_f16, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, s, q, N, K, (uint4 *) out.xm,
+               (uint4 *) out.xs);
     return hipGetLastError();
 }
 

@@ -114,24 +114,21 @@ void Context::init(const llama_context_params & p) {
     aq_ffn.qs = (uint4 *) model.alloc(C * (F / 32) * 16);
     u_ffn = (float *) model.alloc(F * 4);
     {
-        const size_t Cp = (C + 63) / 64 * 64, KX = std::max(E, F);
-        if (model.qtype == F16) {
-            // the Q4 operand images are not needed: f16 activation rows and the f32 Wo input
-            x16 = model.alloc(mm_f16_act_bytes((int) C, (int) KX));
-            LVK_HIP(hipMemset(x16, 0, mm_f16_act_bytes((int) C, (int) KX)));
-            attn_f32 = (float *) model.alloc(C * E * 4);
-        } else {
-            xh = (uint16_t *) model.alloc(mm_act_bytes((int) Cp, (int) KX));
-            LVK_HIP(hipMemset(xh, 0, mm_act_bytes((int) Cp, (int) KX)));   // masked slots stay zero
-            xda = (float *) model.alloc(Cp * (KX / 32) * 4);
-        }
-        if (model.qtype == Q4_1) xside = model.alloc(mm41_act_side_bytes((int) Cp, (int) KX));
+        // xm zeroed once: the masked slots / padding rows are never written (lvk_kernels.h ActImage)
+        auto alloc_image = [&](size_t K) {
+            const ActImageBytes nbytes = act_image_bytes(model.qtype, (int) C, (int) K);
+            ActImage im;
+            im.xm = model.alloc(nbytes.xm);
+            LVK_HIP(hipMemset(im.xm, 0, nbytes.xm));
+            if (nbytes.da) im.da = (float *) model.alloc(nbytes.da);
+            if (nbytes.xs) im.xs = model.alloc(nbytes.xs);
+            return im;
+        };
+        img = alloc_image(std::max(E, F));
         const char * sq = getenv("LVK_MM_SWIGLU_Q");
-        if (model.qtype == Q4_0 && (!sq || atoi(sq) != 0)) {
-            xh2 = (uint16_t *) model.alloc(mm_act_bytes((int) Cp, (int) F));
-            LVK_HIP(hipMemset(xh2, 0, mm_act_bytes((int) Cp, (int) F)));   // masked slots stay zero
-            xda2 = (float *) model.alloc(Cp * (F / 32) * 4);
-        }
+        if (mm_epi_supported(model.qtype, EPI_SWIGLU_Q) && (!sq || atoi(sq) != 0)) img_w2 = alloc_image(F);
+        // f16 weights take the Wo input in f32; the Q4 types take the quantized aq_attn
+        if (model.qtype == F16) attn_f32 = (float *) model.alloc(C * E * 4);
         qkv32 = (float *) model.alloc(C * 3 * E * 4);
         uf = (float *) model.alloc(C * F * 4);
         prompt_exact = getenv("LVK_PROMPT_EXACT") && atoi(getenv("LVK_PROMPT_EXACT")) != 0;
@@ -240,88 +237,6 @@ static double qbytes(const QMatrix & w) {
     return (double) w.M * (w.K / 32) * (w.qtype == Q4_0 ? 20 : 24);
 }
 
-// The forward pass of an f16 model (ggml_compute_forward_mul_mat_f16_f32 where the Q4 path
-// runs mul_mat_q_f32): the same five launches per layer, with the activations converted to
-// f16 (after RMSNorm * g, or plainly for the Wo and W2 inputs, which the attention and the
-// SwiGLU epilogue hand over in f32) instead of quantized.  n == 1: matvec_f16.hip;
-// n > 1: one conversion launch + mm_f16.hip per matrix, RoPE + KV append by launch_rope_kv.
-void Context::enqueue_forward_f16(int n, bool last_only, const int * tok_src, float * logits_out, bool head, bool embed) {
-    const HParams & hp = model.hp;
-    const int E = (int) hp.n_embd, H = (int) hp.n_head, hd = E / H, F = (int) hp.n_ff(), V = (int) hp.n_vocab;
-    const bool seq_ep = seq_epochs;
-    const bool dec_attn = n == 1 && !old_attention && !kv32 && attention_decode_supported(E, H, n_ctx);
-    if (dec_attn && !seq_ep)
-        LVK_HIP(hipMemsetAsync(attn_gran, 0, attention_decode_scratch_bytes(H, n_ctx), stream));
-    if (model.has_embed && embed)
-        timed_launch(K_EMBED, 0, [&] {
-            return launch_embed(model.tok_emb, model.emb_type, E, n == 1 ? &sp_d->pad0 : tok_src, n, x, stream);
-        });
-    auto mm = [&](const QMatrix & w, const float * xin, const float * g, int K, float * y, int ldy, int epi) {
-        EventSplit ev;      // the two kernels are timed as one
-        ev.first();
-        const hipError_t e = launch_act_f16p(xin, g, n, K, x16, stream);
-        if (e != hipSuccess) return e;
-        ev.last();
-        return launch_mm_f16(w, x16, n, y, ldy, epi, silu_tab, stream);
-    };
-    for (size_t il = 0; il < model.layers.size(); ++il) {
-        const Layer & ly = model.layers[il];
-        uint16_t * kcl = kc_layer(il);
-        uint16_t * vcl = vc_layer(il);
-        // the attention kernels also write their quantized output (aq_attn, unused here)
-        AttnLaunch at{q16, kcl, vcl, scores, aq_attn, Q4_0, exp_tab, sp_d, n, E, H, n_ctx};
-        at.out_f32 = attn_f32;
-        at.exp_computed = exp_computed;
-        at.err = err_d;
-        at.kv32 = kv32;
-        at.seq_epochs = seq_ep ? 1 : 0;
-        if (n == 1) {
-            MvLaunch a;
-            a.w = ly.wqkv; a.x = x; a.g = ly.attn_norm; a.sp = sp_d;
-            a.q16 = q16; a.kc = kcl; a.vc = vcl; a.rope.cs = rope;
-            a.n_embd = E; a.head_dim = hd; a.n_ctx = n_ctx; a.kv32 = kv32;
-            timed_launch(K_QKV, qbytes(ly.wqkv), [&] { return launch_matvec_f16(a, PRO_NORM, EPI_QKV, stream); });
-            if (dec_attn)
-                timed_launch(K_ATTN, 0, [&] { return launch_attention_decode(at, attn_gran, (unsigned) il + 1, stream); });
-            else
-                timed_launch(K_ATTN, 0, [&] { return launch_attention(at, stream); });
-            MvLaunch b;
-            b.w = ly.wo; b.x = attn_f32; b.y = x; b.sp = sp_d;
-            timed_launch(K_WO, qbytes(ly.wo), [&] { return launch_matvec_f16(b, PRO_ACTF, EPI_RESID, stream); });
-            MvLaunch c;
-            c.w = ly.w13; c.x = x; c.g = ly.ffn_norm; c.sp = sp_d; c.silu_tab = silu_tab; c.u = u_ffn;
-            timed_launch(K_W13, qbytes(ly.w13), [&] { return launch_matvec_f16(c, PRO_NORM, EPI_SWIGLU_F32, stream); });
-            MvLaunch d;
-            d.w = ly.w2; d.x = u_ffn; d.y = x; d.sp = sp_d;
-            timed_launch(K_W2, qbytes(ly.w2), [&] { return launch_matvec_f16(d, PRO_ACTF, EPI_RESID, stream); });
-        } else {
-            timed_launch(K_QKV, qbytes(ly.wqkv), [&] { return mm(ly.wqkv, x, ly.attn_norm, E, qkv32, 3 * E, EPI_STORE); });
-            timed_launch(K_QKV, 0, [&] {
-                return launch_rope_kv(qkv32, n, E, hd, rope, sp_d, n_ctx, q16, kcl, vcl, stream, kv32);
-            });
-            if (!kv32 && attention_prompt_supported(E, H, n_ctx))
-                timed_launch(K_ATTN, 0, [&] { return launch_attention_prompt(at, (uint16_t *) scores, nullptr, nullptr, stream); });
-            else
-                timed_launch(K_ATTN, 0, [&] { return launch_attention(at, stream); });
-            timed_launch(K_WO, qbytes(ly.wo), [&] { return mm(ly.wo, attn_f32, nullptr, E, x, E, EPI_RESID); });
-            timed_launch(K_W13, qbytes(ly.w13), [&] { return mm(ly.w13, x, ly.ffn_norm, E, uf, F, EPI_SWIGLU_F32); });
-            timed_launch(K_W2, qbytes(ly.w2), [&] { return mm(ly.w2, uf, nullptr, F, x, E, EPI_RESID); });
-        }
-    }
-    if (!model.has_head || !head) return;   // not the last pipeline stage: x is the output
-    if (last_only || n == 1) {
-        MvLaunch o;
-        o.w = model.output; o.x = x; o.g = model.norm; o.sp = sp_d; o.y = logits_out;
-        o.tok0 = n - 1;
-        timed_launch(K_LMHEAD, qbytes(model.output), [&] { return launch_matvec_f16(o, PRO_NORM, EPI_STORE, stream); });
-    } else {
-        // logits_all: lm_head over every row
-        timed_launch(K_LMHEAD, qbytes(model.output), [&] { return mm(model.output, x, model.norm, E, logits_out, V, EPI_STORE); });
-    }
-    if (want_embedding)
-        LVK_HIP(launch_rmsnorm_rows(x + (size_t) (n - 1) * E, model.norm, E, 1, emb_d, stream));
-}
-
 // decode kernels: the CU-balanced path (matvec_cu.hip) where its row length is
 // compiled in, else the generic kernel
 static hipError_t mv_launch(const MvLaunch & L, int pro, int epi, hipStream_t s) {
@@ -332,113 +247,34 @@ static hipError_t mv_launch(const MvLaunch & L, int pro, int epi, hipStream_t s)
     return launch_matvec(L, pro, epi, s);
 }
 
-// prompt batches go through the MFMA matmuls when every matrix of the model fits them
-bool Context::use_mfma(int n) const {
-    // below 16 tokens the per-row VALU kernels win (the MFMA tile is 16 tokens wide)
-    if (n < 16 || prompt_exact) return false;
+// batches go through the batched matmuls (launch_act + launch_mm) when every matrix of the
+// model fits them: f16 weights from 2 tokens on (their matvec is single-token only), the Q4
+// types from 16 (the MFMA tile is 16 tokens wide; below that the per-row VALU kernels win)
+bool Context::use_batched(int n) const {
+    if (n == 1 || (model.qtype != F16 && (n < 16 || prompt_exact))) return false;
     for (const Layer & ly : model.layers)
-        if (!mm_mfma_supported(ly.wqkv) || !mm_mfma_supported(ly.wo) || !mm_mfma_supported(ly.w13) ||
-            !mm_mfma_supported(ly.w2))
+        if (!mm_supported(ly.wqkv) || !mm_supported(ly.wo) || !mm_supported(ly.w13) || !mm_supported(ly.w2))
             return false;
     return true;
 }
 
+// The layer sequence, the same for every weight type (f16 weights:
+// ggml_compute_forward_mul_mat_f16_f32 where the Q4 types run mul_mat_q_f32; the activations are
+// converted to f16 where the Q4 types quantize them):
+//   embed, then per layer norm -> QKV, RoPE + KV append, attention, Wo (+x),
+//   norm -> W1|W3 (SwiGLU), W2 (+x), then the head.
+// Batches (use_batched) run it as operand image + matmul per matrix, everything else as one
+// matvec launch per matrix with the conversion in its prologue.
 void Context::enqueue_forward(int n, bool last_only, const int * tok_src, int logit_row, bool head, bool embed) {
     const HParams & hp = model.hp;
     if (!tok_src) tok_src = tok_d;
     float * const logits_out = logits_d + (size_t) logit_row * hp.n_vocab;
-    const int E = (int) hp.n_embd, H = (int) hp.n_head, hd = E / H, F = (int) hp.n_ff();
-    if (model.qtype == F16) {
-        enqueue_forward_f16(n, last_only, tok_src, logits_out, head, embed);
-        return;
-    }
-    if (use_mfma(n)) {
-        // prompt batch on the matrix cores: per layer
-        //   act(norm) -> QKV (store) -> RoPE + KV append -> attention -> act -> Wo (+x)
-        //   act(norm) -> W1|W3 (silu * mul) -> act -> W2 (+x)
-        // Q4_0: mm_mfma.hip (activation scales da); Q4_1: mm_mfma41.hip (side image xs)
-        const bool q41 = model.qtype == Q4_1;
-        auto act = [&](const float * xin, const float * g, int K) {
-            return q41 ? launch_act41_f16(xin, g, n, K, xh, xside, stream) : launch_act_f16(xin, g, n, K, xh, xda, stream);
-        };
-        auto mm = [&](const QMatrix & w, float * y, int ldy, int epi, const uint16_t * st) {
-            return q41 ? launch_mm_mfma41(w, xh, xside, n, y, ldy, epi, st, stream)
-                       : launch_mm_mfma(w, xh, xda, n, y, ldy, 0, epi, st, stream);
-        };
-        if (model.has_embed)
-            timed_launch(K_EMBED, 0, [&] { return launch_embed(model.tok_emb, model.emb_type, E, tok_src, n, x, stream); });
-        for (size_t il = 0; il < model.layers.size(); ++il) {
-            const Layer & ly = model.layers[il];
-            uint16_t * kcl = kc_layer(il);
-            uint16_t * vcl = vc_layer(il);
-            timed_launch(K_QKV, 0, [&] { return act(x, ly.attn_norm, E); });
-            if (!kv32 && mm_rope_fused) {
-                // RoPE + KV append in the matmul's epilogue (the f32 rows never reach memory)
-                const RopeKV rk{rope, sp_d, n_ctx, E, hd, q16, kcl, vcl};
-                timed_launch(K_QKV, qbytes(ly.wqkv), [&] {
-                    return q41 ? launch_mm_mfma41(ly.wqkv, xh, xside, n, nullptr, 0, EPI_ROPE_KV, nullptr, stream, &rk)
-                               : launch_mm_qkv_rope(ly.wqkv, xh, xda, n, rk, stream);
-                });
-            } else {
-                timed_launch(K_QKV, qbytes(ly.wqkv), [&] { return mm(ly.wqkv, qkv32, 3 * E, EPI_STORE, nullptr); });
-                timed_launch(K_QKV, 0, [&] {
-                    return launch_rope_kv(qkv32, n, E, hd, rope, sp_d, n_ctx, q16, kcl, vcl, stream, kv32);
-                });
-            }
-            AttnLaunch at{q16, kcl, vcl, scores, aq_attn, model.qtype, exp_tab, sp_d, n, E, H, n_ctx};
-            at.exp_computed = exp_computed;
-            at.err = err_d;
-            at.kv32 = kv32;
-            if (!kv32 && attention_prompt_supported(E, H, n_ctx)) {
-                // writes the Wo input in both forms (ActQ and the MFMA operand images)
-                timed_launch(K_ATTN, 0, [&] {
-                    return q41 ? launch_attention_prompt(at, (uint16_t *) scores, xh, nullptr, stream, xside)
-                               : launch_attention_prompt(at, (uint16_t *) scores, xh, xda, stream);
-                });
-            } else {
-                timed_launch(K_ATTN, 0, [&] { return launch_attention(at, stream); });
-                timed_launch(K_WO, 0, [&] {
-                    return q41 ? launch_actq41_to_f16(aq_attn, n, E, xh, xside, stream)
-                               : launch_actq_to_f16(aq_attn, n, E, xh, xda, stream);
-                });
-            }
-            timed_launch(K_WO, qbytes(ly.wo), [&] { return mm(ly.wo, x, E, EPI_RESID, nullptr); });
-            timed_launch(K_W13, 0, [&] { return act(x, ly.ffn_norm, E); });
-            if (!q41 && xh2) {
-                // SwiGLU + the W2 input's quantization in the W1|W3 epilogue
-                timed_launch(K_W13, qbytes(ly.w13), [&] {
-                    return launch_mm_w13_q(ly.w13, xh, xda, n, silu_tab, xh2, xda2, stream);
-                });
-                timed_launch(K_W2, qbytes(ly.w2), [&] {
-                    return launch_mm_mfma(ly.w2, xh2, xda2, n, x, E, 0, EPI_RESID, nullptr, stream);
-                });
-            } else {
-                timed_launch(K_W13, qbytes(ly.w13), [&] { return mm(ly.w13, uf, F, EPI_SWIGLU_F32, silu_tab); });
-                timed_launch(K_W2, 0, [&] { return act(uf, nullptr, F); });
-                timed_launch(K_W2, qbytes(ly.w2), [&] { return mm(ly.w2, x, E, EPI_RESID, nullptr); });
-            }
-        }
-        if (!model.has_head || !head) return;
-        if (last_only || !mm_mfma_supported(model.output)) {
-            MvLaunch o;
-            o.w = model.output; o.x = x; o.g = model.norm; o.sp = sp_d; o.y = logits_out;
-            o.tok0 = last_only ? n - 1 : 0;
-            o.n_tokens = last_only ? 1 : n;
-            timed_launch(K_LMHEAD, qbytes(model.output), [&] { return mv_launch(o, PRO_NORM, EPI_STORE, stream); });
-        } else {
-            timed_launch(K_LMHEAD, 0, [&] { return act(x, model.norm, E); });
-            timed_launch(K_LMHEAD, qbytes(model.output), [&] {
-                return mm(model.output, logits_out, (int) hp.n_vocab, EPI_STORE, nullptr);
-            });
-        }
-        if (want_embedding)
-            LVK_HIP(launch_rmsnorm_rows(x + (size_t) (n - 1) * E, model.norm, E, 1, emb_d, stream));
-        return;
-    }
-    // single-token FFN: W1|W3 hands silu(w1 x)*(w3 x) to W2 in f32, W2 quantizes it
-    const bool ffn_f32 = n == 1 && matvec_cu_supported(E, model.qtype) && matvec_cu_supported(F, model.qtype);
-    const bool seq_ep = seq_epochs;
-    if (n == 1 && !old_attention && attention_decode_supported(E, H, n_ctx) && !seq_ep)
+    const int E = (int) hp.n_embd, H = (int) hp.n_head, hd = E / H, F = (int) hp.n_ff(), V = (int) hp.n_vocab;
+    const int qt = model.qtype;
+    const bool batched = use_batched(n);
+    const bool prompt_attn = n > 1 && !kv32 && attention_prompt_supported(E, H, n_ctx);
+    const bool decode_attn = n == 1 && !old_attention && !kv32 && attention_decode_supported(E, H, n_ctx);
+    if (decode_attn && !seq_epochs)
         // the decode attention's score granules carry epoch = layer + 1: zero them once per token
         LVK_HIP(hipMemsetAsync(attn_gran, 0, attention_decode_scratch_bytes(H, n_ctx), stream));
     if (model.has_embed && embed)
@@ -446,27 +282,80 @@ void Context::enqueue_forward(int n, bool last_only, const int * tok_src, int lo
         timed_launch(K_EMBED, 0, [&] {
             return launch_embed(model.tok_emb, model.emb_type, E, n == 1 ? &sp_d->pad0 : tok_src, n, x, stream);
         });
+    // x[n][K] (rms_norm * g when g) -> img, and y = / += W img
+    auto act = [&](int cls, const float * xin, const float * g, int K) {
+        timed_launch(cls, 0, [&] { return launch_act(qt, xin, g, n, K, img, stream); });
+    };
+    auto mm = [&](int cls, const QMatrix & w, const ActImage & in, float * y, int ldy, int epi, const RopeKV * rk = nullptr,
+                  const ActImage & out = {}) {
+        MmLaunch L;
+        L.w = w; L.x = in; L.N = n; L.y = y; L.ldy = ldy; L.silu_tab = silu_tab; L.rk = rk; L.out = out;
+        timed_launch(cls, qbytes(w), [&] { return launch_mm(L, epi, stream); });
+    };
+    // single-token FFN: W1|W3 hands silu(w1 x)*(w3 x) to W2 in f32, W2 converts it
+    const bool ffn_f32 = n == 1 && matvec_cu_supported(E, qt) && matvec_cu_supported(F, qt);
     for (size_t il = 0; il < model.layers.size(); ++il) {
         const Layer & ly = model.layers[il];
-        MvLaunch a;
-        a.w = ly.wqkv; a.x = x; a.g = ly.attn_norm; a.sp = sp_d; a.n_tokens = n;
-        a.q16 = q16; a.kc = kc_layer(il); a.vc = vc_layer(il); a.rope.cs = rope;
-        a.n_embd = E; a.head_dim = hd; a.n_ctx = n_ctx; a.kv32 = kv32;
-        AttnLaunch at{q16, kc_layer(il), vc_layer(il), scores, aq_attn, model.qtype, exp_tab, sp_d, n, E, H, n_ctx};
+        uint16_t * kcl = kc_layer(il);
+        uint16_t * vcl = vc_layer(il);
+        // every attention kernel writes the Wo input quantized (aq_attn; Q4_0 blocks for an f16
+        // model, which reads attn_f32 instead)
+        AttnLaunch at{q16, kcl, vcl, scores, aq_attn, qt == F16 ? Q4_0 : qt, exp_tab, sp_d, n, E, H, n_ctx};
+        at.out_f32 = attn_f32;
         at.exp_computed = exp_computed;
         at.err = err_d;
         at.kv32 = kv32;
-        at.seq_epochs = seq_ep ? 1 : 0;
+        at.seq_epochs = seq_epochs ? 1 : 0;
+        if (batched) {
+            act(K_QKV, x, ly.attn_norm, E);
+            if (!kv32 && mm_rope_fused && mm_epi_supported(qt, EPI_ROPE_KV)) {
+                // RoPE + KV append in the matmul's epilogue (the f32 rows never reach memory)
+                const RopeKV rk{rope, sp_d, n_ctx, E, hd, q16, kcl, vcl};
+                mm(K_QKV, ly.wqkv, img, nullptr, 0, EPI_ROPE_KV, &rk);
+            } else {
+                mm(K_QKV, ly.wqkv, img, qkv32, 3 * E, EPI_STORE);
+                timed_launch(K_QKV, 0, [&] {
+                    return launch_rope_kv(qkv32, n, E, hd, rope, sp_d, n_ctx, q16, kcl, vcl, stream, kv32);
+                });
+            }
+            // the Wo input image: written by the prompt attention itself (Q4), else from the
+            // attention's f32 rows (f16 weights) or its quantized blocks
+            const bool wo_fused = prompt_attn && !attn_f32;
+            if (prompt_attn)
+                timed_launch(K_ATTN, 0, [&] {
+                    return launch_attention_prompt(at, (uint16_t *) scores, wo_fused ? img : ActImage{}, stream);
+                });
+            else
+                timed_launch(K_ATTN, 0, [&] { return launch_attention(at, stream); });
+            if (attn_f32) act(K_WO, attn_f32, nullptr, E);
+            else if (!wo_fused) timed_launch(K_WO, 0, [&] { return launch_actq_to_image(qt, aq_attn, n, E, img, stream); });
+            mm(K_WO, ly.wo, img, x, E, EPI_RESID);
+            act(K_W13, x, ly.ffn_norm, E);
+            if (img_w2.xm) {
+                // SwiGLU + the W2 input's quantization in the W1|W3 epilogue
+                mm(K_W13, ly.w13, img, nullptr, 0, EPI_SWIGLU_Q, nullptr, img_w2);
+                mm(K_W2, ly.w2, img_w2, x, E, EPI_RESID);
+            } else {
+                mm(K_W13, ly.w13, img, uf, F, EPI_SWIGLU_F32);
+                act(K_W2, uf, nullptr, F);
+                mm(K_W2, ly.w2, img, x, E, EPI_RESID);
+            }
+            continue;
+        }
+        MvLaunch a;
+        a.w = ly.wqkv; a.x = x; a.g = ly.attn_norm; a.sp = sp_d; a.n_tokens = n;
+        a.q16 = q16; a.kc = kcl; a.vc = vcl; a.rope.cs = rope;
+        a.n_embd = E; a.head_dim = hd; a.n_ctx = n_ctx; a.kv32 = kv32;
         timed_launch(K_QKV, qbytes(ly.wqkv), [&] { return mv_launch(a, PRO_NORM, EPI_QKV, stream); });
-        if (n > 1 && !kv32 && attention_prompt_supported(E, H, n_ctx))
-            timed_launch(K_ATTN, 0, [&] { return launch_attention_prompt(at, (uint16_t *) scores, nullptr, nullptr, stream); });
-        else if (n == 1 && !old_attention && !kv32 && attention_decode_supported(E, H, n_ctx))
+        if (prompt_attn)
+            timed_launch(K_ATTN, 0, [&] { return launch_attention_prompt(at, (uint16_t *) scores, ActImage{}, stream); });
+        else if (decode_attn)
             timed_launch(K_ATTN, 0, [&] { return launch_attention_decode(at, attn_gran, (unsigned) il + 1, stream); });
         else
             timed_launch(K_ATTN, 0, [&] { return launch_attention(at, stream); });
-        MvLaunch b;
-        b.w = ly.wo; b.xq = aq_attn; b.y = x; b.sp = sp_d; b.n_tokens = n;
-        timed_launch(K_WO, qbytes(ly.wo), [&] { return mv_launch(b, PRO_ACTQ, EPI_RESID, stream); });
+        MvLaunch b;      // input: the attention's f32 rows (f16 weights) or its quantized blocks
+        b.w = ly.wo; b.x = attn_f32; b.xq = aq_attn; b.y = x; b.sp = sp_d; b.n_tokens = n;
+        timed_launch(K_WO, qbytes(ly.wo), [&] { return mv_launch(b, attn_f32 ? PRO_ACTF : PRO_ACTQ, EPI_RESID, stream); });
         MvLaunch c;
         c.w = ly.w13; c.x = x; c.g = ly.ffn_norm; c.sp = sp_d; c.n_tokens = n; c.silu_tab = silu_tab;
         c.out_q = aq_ffn; c.u = u_ffn;
@@ -481,12 +370,18 @@ void Context::enqueue_forward(int n, bool last_only, const int * tok_src, int lo
         }
     }
     if (!model.has_head || !head) return;   // not the last pipeline stage: x is the output
-    MvLaunch o;
-    o.w = model.output; o.x = x; o.g = model.norm; o.sp = sp_d; o.y = logits_out;
-    o.tok0 = last_only ? n - 1 : 0;
-    o.n_tokens = last_only ? 1 : n;
-    timed_launch(K_LMHEAD, qbytes(model.output), [&] { return mv_launch(o, PRO_NORM, EPI_STORE, stream); });
-    if (want_embedding && model.has_head)
+    if (batched && !last_only && mm_supported(model.output)) {
+        // logits_all: lm_head over every row
+        act(K_LMHEAD, x, model.norm, E);
+        mm(K_LMHEAD, model.output, img, logits_out, V, EPI_STORE);
+    } else {
+        MvLaunch o;
+        o.w = model.output; o.x = x; o.g = model.norm; o.sp = sp_d; o.y = logits_out;
+        o.tok0 = last_only ? n - 1 : 0;
+        o.n_tokens = last_only ? 1 : n;
+        timed_launch(K_LMHEAD, qbytes(model.output), [&] { return mv_launch(o, PRO_NORM, EPI_STORE, stream); });
+    }
+    if (want_embedding)
         LVK_HIP(launch_rmsnorm_rows(x + (size_t) (n - 1) * E, model.norm, E, 1, emb_d, stream));
 }
 

@@ -100,22 +100,19 @@ struct Context {
     bool prompt_exact = false;
     bool old_attention = false;  // env LVK_ATTN_V1=1: single-token evals on the one-kernel attention.hip
     void * attn_gran = nullptr;  // [H][n_ctx] {tag, score} granules of the decode attention
-    uint16_t * xh = nullptr;     // masked MFMA B-fragment image of the quantized activations (mm_act_bytes)
-    float * xda = nullptr;       // [Cpad][max(E,F)/32] their block scales
-    // Q4_0 prompt: the W2 input image written by the W1|W3 epilogue (EPI_SWIGLU_Q; the W1|W3
-    // launch still reads xh); LVK_MM_SWIGLU_Q=0: f32 uf + k_act_q40_f16_tile instead
-    uint16_t * xh2 = nullptr;
-    float * xda2 = nullptr;
-    void * xside = nullptr;      // Q4_1: the activations' side image (mm41_act_side_bytes)
-    float * qkv32 = nullptr;     // [C][3E] Q|K|V rows before RoPE (f32-KV prompts, LVK_MM_ROPE=0)
+    // batched (N > 1) matmuls: the operand image of the matrix about to run (lvk_kernels.h
+    // ActImage, sized for n_ctx rows of max(E, F)), rewritten before every matmul
+    ActImage img;
+    // Q4_0: the W2 input image written by the W1|W3 epilogue (EPI_SWIGLU_Q; the W1|W3 launch
+    // still reads img); LVK_MM_SWIGLU_Q=0: f32 uf + launch_act instead
+    ActImage img_w2;
+    float * qkv32 = nullptr;     // [C][3E] Q|K|V rows before RoPE (f32-KV prompts, LVK_MM_ROPE=0, f16 models)
     // prompt: RoPE + KV append fused into the QKV matmul (LVK_MM_ROPE=0: separate kernel)
     bool mm_rope_fused = [] { const char * e = getenv("LVK_MM_ROPE"); return !e || atoi(e) != 0; }();
     float * uf = nullptr;        // [C][F] silu(w1 x) * (w3 x)
-    // f16 models (model.qtype == F16): the attention's f32 output (the Wo input, converted
-    // to f16 by the matmul's prologue) and the prompt matmuls' f16 activation rows
+    // f16 models (model.qtype == F16) only: the attention's f32 output, the Wo input (converted
+    // to f16 by launch_act / the matvec's prologue); nullptr = Wo takes the quantized aq_attn
     float * attn_f32 = nullptr;  // [C][E]
-    void * x16 = nullptr;        // mm_f16_act_bytes(C, max(E, F))
-    void enqueue_forward_f16(int n, bool last_only, const int * tok_src, float * logits_out, bool head, bool embed);
 
     // decode graph (N = 1, last-token logits)
     hipGraph_t graph = nullptr;
@@ -194,7 +191,7 @@ struct Context {
     void x_copy(void * buf, int n, bool to_ctx, bool on_device);
     void enqueue_forward(int n, bool last_only, const int * tok_src = nullptr, int logit_row = 0, bool head = true,
                          bool embed = true);
-    bool use_mfma(int n) const;
+    bool use_batched(int n) const;
     void build_graph(int kind = 0);      // 0 logits, 1 greedy, 2 sample, 3 chained greedy step
     int eval_greedy(int token, int n_past);
     void kv_get();

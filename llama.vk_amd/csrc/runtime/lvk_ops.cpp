@@ -140,6 +140,19 @@ int lvk_mul_mat_q_norm(int type, const void * w, int m, int k, const float * g, 
     catch (const lvk::Error & e) { return fail(__func__, e.msg); }
 }
 
+// y[n][M] = W . act(x) through the batched interface: operand image (xm zeroed once), then the matmul
+static void mm_batched(Dev & dv, const lvk::QMatrix & q, const float * xd, const float * gd, int n, float * yd) {
+    const lvk::ActImageBytes nbytes = lvk::act_image_bytes(q.qtype, n, q.K);
+    lvk::MmLaunch L;
+    L.w = q; L.N = n; L.y = yd; L.ldy = q.M;
+    L.x.xm = dv.get(nbytes.xm);
+    LVK_HIP(hipMemset(L.x.xm, 0, nbytes.xm));
+    if (nbytes.da) L.x.da = (float *) dv.get(nbytes.da);
+    if (nbytes.xs) L.x.xs = dv.get(nbytes.xs);
+    LVK_HIP(lvk::launch_act(q.qtype, xd, gd, n, q.K, L.x, nullptr));
+    LVK_HIP(lvk::launch_mm(L, lvk::EPI_STORE, nullptr));
+}
+
 int lvk_mul_mat_q_mfma(int type, const void * w, int m, int k, const float * g, const float * x, int n, float * y) {
     try {
         if (type != lvk::Q4_0 && type != lvk::Q4_1) return fail(__func__, "Q4_0 / Q4_1 only");
@@ -162,18 +175,8 @@ int lvk_mul_mat_q_mfma(int type, const void * w, int m, int k, const float * g, 
         }
         float * xd = dv.up(x, (size_t) n * k);
         const float * gd = g ? dv.up(g, (size_t) k) : nullptr;
-        void * xh = dv.get(lvk::mm_act_bytes(n, k));
-        LVK_HIP(hipMemset(xh, 0, lvk::mm_act_bytes(n, k)));
         float * yd = (float *) dv.get((size_t) n * m * 4);
-        if (type == lvk::Q4_1) {
-            void * xs = dv.get(lvk::mm41_act_side_bytes(n, k));
-            LVK_HIP(lvk::launch_act41_f16(xd, gd, n, k, xh, xs, nullptr));
-            LVK_HIP(lvk::launch_mm_mfma41(q, xh, xs, n, yd, m, lvk::EPI_STORE, nullptr, nullptr));
-        } else {
-            float * da = (float *) dv.get((size_t) n * nb * 4);
-            LVK_HIP(lvk::launch_act_f16(xd, gd, n, k, xh, da, nullptr));
-            LVK_HIP(lvk::launch_mm_mfma(q, xh, da, n, yd, m, 0, lvk::EPI_STORE, nullptr, nullptr));
-        }
+        mm_batched(dv, q, xd, gd, n, yd);
         LVK_HIP(hipMemcpy(y, yd, (size_t) n * m * 4, hipMemcpyDeviceToHost));
         return 0;
     } catch (const lvk::Error & e) { return fail(__func__, e.msg); }
@@ -199,10 +202,7 @@ int lvk_mul_mat_f16(const uint16_t * w, int m, int k, const float * g, const flo
             L.w = q; L.x = xd; L.g = gd; L.sp = dv.up(&sp, 1); L.y = yd;
             LVK_HIP(lvk::launch_matvec_f16(L, g ? lvk::PRO_NORM : lvk::PRO_ACTF, lvk::EPI_STORE, nullptr));
         } else {
-            void * x16 = dv.get(lvk::mm_f16_act_bytes(n, k));
-            LVK_HIP(hipMemset(x16, 0, lvk::mm_f16_act_bytes(n, k)));
-            LVK_HIP(lvk::launch_act_f16p(xd, gd, n, k, x16, nullptr));
-            LVK_HIP(lvk::launch_mm_f16(q, x16, n, yd, m, lvk::EPI_STORE, nullptr, nullptr));
+            mm_batched(dv, q, xd, gd, n, yd);
         }
         LVK_HIP(hipMemcpy(y, yd, (size_t) n * m * 4, hipMemcpyDeviceToHost));
         return 0;
@@ -268,7 +268,7 @@ static int attention_impl(const uint16_t * kc, const uint16_t * vc, const float 
         uint16_t * pd = nullptr;
         if (scores_out) pd = (uint16_t *) dv.get((size_t) n * n_head * n_ctx * 2);
         A.p16_out = pd;
-        if (kind == 1) LVK_HIP(lvk::launch_attention_prompt(A, (uint16_t *) A.scores, nullptr, nullptr, nullptr));
+        if (kind == 1) LVK_HIP(lvk::launch_attention_prompt(A, (uint16_t *) A.scores, lvk::ActImage{}, nullptr));
         else if (kind == 2) {
             void * gran = dv.get(lvk::attention_decode_scratch_bytes(n_head, n_ctx));
             LVK_HIP(hipMemset(gran, 0, lvk::attention_decode_scratch_bytes(n_head, n_ctx)));

@@ -109,19 +109,20 @@ def test_13b_q4_1_long_context_2048_vs_reference(model13b, ref):
         rm.close()
 
 
-def test_prompt_image_bytes_follow_the_capacity_rule(model13b):
+def test_prompt_image_bytes_follow_the_capacity_rule(model13b, monkeypatch):
     """lvk_prompt_image_bytes: the Q4_1 f16 + side images (3 B per weight of the layer matrices
     and the lm_head) are built for 13B; LVK_PROMPT_A16=0 builds none"""
     import lvk
     E, F, L, V = 5120, 13824, 40, 32000
     m = lvk.Llama(model13b, n_ctx=64)
-    got = m.prompt_image_bytes()
-    m.close()
-    assert got >= 3 * (L * (4 * E * E + 3 * E * F)), got
-    os.environ["LVK_PROMPT_A16"] = "0"
     try:
-        m = lvk.Llama(model13b, n_ctx=64)
-        assert m.prompt_image_bytes() == 0
-        m.close()
+        got = m.prompt_image_bytes()
     finally:
-        del os.environ["LVK_PROMPT_A16"]
+        m.close()
+    assert got >= 3 * (L * (4 * E * E + 3 * E * F)), got
+    monkeypatch.setenv("LVK_PROMPT_A16", "0")
+    m = lvk.Llama(model13b, n_ctx=64)
+    try:
+        assert m.prompt_image_bytes() == 0
+    finally:
+        m.close()

@@ -231,7 +231,7 @@ def test_mfma_prompt_13b_q4_1_shaped_vs_oracle(lvk, oracle, model_dir, monkeypat
     prompt (ragged token tile) through the Q4_1 MFMA matmuls (mm_mfma41.hip), then decode on
     the KV cache it wrote, bit-exact against the oracle.  The Wo input comes from the prompt
     attention's fused Q4_1 epilogue (n_ctx 256) or from the generic attention's ActQ via
-    launch_actq41_to_f16 (n_ctx 2048, past the prompt attention's LDS window); RoPE + KV append
+    launch_actq_to_image (n_ctx 2048, past the prompt attention's LDS window); RoPE + KV append
     in the QKV matmul's epilogue (default) or by k_rope_kv (LVK_MM_ROPE=0)"""
     from oracle_lib import gen_model
     path = gen_model(os.path.join(model_dir, "w5120_l2_q41.bin"), n_embd=5120, n_head=40, n_layer=2, ftype=3, seed=11)

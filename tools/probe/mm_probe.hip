@@ -28,9 +28,11 @@ int main(int argc, char ** argv) {
     const int KX = 11008;
     float * x = (float *) dalloc((size_t) N * KX * 4);
     hipLaunchKernelGGL(k_fill_f32, dim3(1024), dim3(256), 0, 0, x, (size_t) N * KX, -2.f, 2.f, 3u);
-    void * xh = dalloc(mm_act_bytes(N, KX));
-    CK(hipMemset(xh, 0, mm_act_bytes(N, KX)));
-    float * da = (float *) dalloc((size_t) N * KX / 32 * 4);
+    const ActImageBytes ib = act_image_bytes(Q4_0, N, KX);
+    ActImage img;
+    img.xm = dalloc(ib.xm);
+    CK(hipMemset(img.xm, 0, ib.xm));
+    img.da = (float *) dalloc(ib.da);
     float * y = (float *) dalloc((size_t) N * 22016 * 4);
     uint16_t * stab = (uint16_t *) dalloc(65536 * 2);
     CK(hipMemset(stab, 0, 65536 * 2));
@@ -48,11 +50,13 @@ int main(int argc, char ** argv) {
             CK(launch_build_a16(q, a16, 0));
             q.a16 = a16;
         }
-        CK(launch_act_f16(x, nullptr, N, s.K, xh, da, 0));
-        const int ldy = s.epi == EPI_SWIGLU_F32 ? s.M / 2 : s.M;
+        CK(launch_act(Q4_0, x, nullptr, N, s.K, img, 0));
+        MmLaunch L;
+        L.w = q; L.x = img; L.N = N; L.y = y; L.ldy = s.epi == EPI_SWIGLU_F32 ? s.M / 2 : s.M; L.silu_tab = stab;
+        const int ldy = L.ldy;
         // one launch on a zeroed y: FNV hash of the output bits (variants must agree)
         CK(hipMemset(y, 0, (size_t) N * ldy * 4));
-        CK(launch_mm_mfma(q, xh, da, N, y, ldy, 0, s.epi, stab, 0));
+        CK(launch_mm(L, s.epi, 0));
         CK(hipDeviceSynchronize());
         {
             std::vector<uint32_t> h((size_t) N * ldy);
@@ -61,10 +65,10 @@ int main(int argc, char ** argv) {
             for (uint32_t v : h) { f ^= v; f *= 1099511628211ull; }
             printf("%-4s hash %016llx\n", s.name, (unsigned long long) f);
         }
-        for (int i = 0; i < 2; ++i) CK(launch_mm_mfma(q, xh, da, N, y, ldy, 0, s.epi, stab, 0));
+        for (int i = 0; i < 2; ++i) CK(launch_mm(L, s.epi, 0));
         CK(hipDeviceSynchronize());
         CK(hipEventRecord(e0, 0));
-        for (int i = 0; i < reps; ++i) CK(launch_mm_mfma(q, xh, da, N, y, s.epi == EPI_SWIGLU_F32 ? s.M / 2 : s.M, 0, s.epi, stab, 0));
+        for (int i = 0; i < reps; ++i) CK(launch_mm(L, s.epi, 0));
         CK(hipEventRecord(e1, 0)); CK(hipEventSynchronize(e1));
         float ms; CK(hipEventElapsedTime(&ms, e0, e1));
         const double us = ms * 1e3 / reps;
