@@ -107,7 +107,6 @@ struct MvLaunch {
     const StepParams * sp = nullptr; // device step params (n_past, n_tokens)
     int n_tokens = 1;                // host-known token count of this launch
     int tok0 = 0;                    // first token row of x / xq to use
-    int out_tok0 = 0;                // first output row to write
     // outputs
     float * y = nullptr;             // EPI_STORE: [N][M];  EPI_RESID: residual [N][M] (in place)
     // EPI_QKV
@@ -123,7 +122,9 @@ struct MvLaunch {
     float * u = nullptr;                   // EPI_SWIGLU_F32: u in f32 [N][M/2]
 };
 
-// dispatches on L.w.qtype: Q4_0 here (matvec_q4.hip), Q4_1 and F16 forwarded
+// dispatches on L.w.qtype: Q4_0 here (matvec_q4.hip), Q4_1 and F16 forwarded.  Every matvec
+// launcher returns hipErrorNotSupported for a (pro, epi) pair it has no instantiation for and
+// hipErrorInvalidValue when the input that pro reads (x, g, or xq.qs / xq.d / xq.m) is null.
 hipError_t launch_matvec(const MvLaunch & L, int pro, int epi, hipStream_t s);
 // the same for Q4_1 weights (matvec_q41.hip)
 hipError_t launch_matvec_q41(const MvLaunch & L, int pro, int epi, hipStream_t s);
@@ -134,8 +135,16 @@ hipError_t launch_matvec_q41(const MvLaunch & L, int pro, int epi, hipStream_t s
 // Returns hipErrorNotSupported for anything else (the caller then uses launch_matvec).
 bool matvec_cu_supported(int K, int qtype = Q4_0);
 hipError_t launch_matvec_cu(const MvLaunch & L, int pro, int epi, hipStream_t s);
-bool matvec_cu41_supported(int K);
-hipError_t launch_matvec_cu41(const MvLaunch & L, int pro, int epi, hipStream_t s);
+// the rule of every caller that takes either: a single token of a compiled-in row length goes
+// to the CU-balanced kernel, everything else (and what that has no instantiation for) to the
+// generic one
+inline hipError_t launch_matvec_auto(const MvLaunch & L, int pro, int epi, hipStream_t s) {
+    if (L.n_tokens == 1 && matvec_cu_supported(L.w.K, L.w.qtype)) {
+        const hipError_t e = launch_matvec_cu(L, pro, epi, s);
+        if (e != hipErrorNotSupported) return e;
+    }
+    return launch_matvec(L, pro, epi, s);
+}
 // compute units of the current device (one decode workgroup per CU)
 int cu_count();
 

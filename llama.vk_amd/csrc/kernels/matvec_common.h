@@ -1,10 +1,16 @@
-// matvec_common.h -- device helpers shared by the Q4_0 matvec kernels
-// (activation table in LDS, reference Q4_0 quantizer pieces, octet reduce).
+// matvec_common.h -- what the matvec kernels share: the argument block, the activation tables
+// in LDS with their prologue pieces (reference Q4_0 / Q4_1 quantizers), the octet reduce and
+// the epilogues.
 #pragma once
 #include "lvk_device.h"
 #include "lvk_kernels.h"
 
 namespace lvk {
+
+// the Q4_1 half of matvec_cu_supported / launch_matvec_cu (matvec_cu41.hip)
+bool matvec_cu41_supported(int K);
+hipError_t launch_matvec_cu41(const MvLaunch & L, int pro, int epi, hipStream_t s);
+
 namespace mv {
 
 // Marks loaded values as produced here for hipcc's wait-count pass.  A load whose result is
@@ -214,22 +220,214 @@ __device__ __forceinline__ uint32_t wsum_word(uint32_t w, bool other, uint32_t s
     return ((other ? mir : t) >> shift) & 0x00FF00FFu;
 }
 
-// QKV epilogue of both decode matvecs, per output row (lane row r of an 8-row group, chain
-// lane j): RoPE mode 0 on q and k (ggml.c:7209-7223; rows e and e^1 are lanes l and l^8),
-// the q row / K-cache row / V-cache column stores (llama.cpp:996-1008).
-__device__ __forceinline__ void qkv_epilogue(float res, int row, int j, int E, int hd, int pos,
-                                             const float2 * rope, uint16_t * q16, uint16_t * kc, uint16_t * vc,
-                                             int n_ctx, int kv32) {
+// ---- the arguments every matvec kernel takes.  A kernel's parameter block is this plus what
+// only it needs: its weight images and extents (and, for the generic kernels of matvec_q4.hip /
+// matvec_q41.hip, the token window and the quantized output).
+struct MvArgs {
+    const float * x;            // PRO_NORM / PRO_ACTF: f32 input
+    const float * g;            // PRO_NORM: norm weight [K]
+    ActQ xq;                    // PRO_ACTQ: quantized input
+    const StepParams * sp;
+    float * y;                  // EPI_STORE / EPI_RESID
+    float * u;                  // EPI_SWIGLU_F32: silu(w1 x) * (w3 x) [M/2]
+    uint16_t * q16;
+    uint16_t * kc;
+    uint16_t * vc;
+    const float2 * rope;
+    int n_embd, head_dim, n_ctx;
+    int kv32;                   // f32 KV cache and queries (f16_kv = false)
+    const uint16_t * silu_tab;
+};
+
+// at_tok0: the single-token kernels take their inputs advanced to token L.tok0 (every input
+// pointer that is set); the generic kernels index the token window themselves
+inline void mv_fill(MvArgs & A, const MvLaunch & L, bool at_tok0) {
+    const size_t t = at_tok0 ? (size_t) L.tok0 : 0;
+    A.x = L.x ? L.x + t * L.w.K : nullptr;
+    A.g = L.g;
+    A.xq = L.xq;
+    if (A.xq.qs) A.xq.qs += t * L.xq.nb;
+    if (A.xq.d) A.xq.d += t * L.xq.nb;
+    if (A.xq.m) A.xq.m += t * L.xq.nb;
+    A.sp = L.sp;
+    A.y = L.y;
+    A.u = L.u;
+    A.q16 = L.q16; A.kc = L.kc; A.vc = L.vc; A.rope = L.rope.cs;
+    A.n_embd = L.n_embd; A.head_dim = L.head_dim; A.n_ctx = L.n_ctx; A.kv32 = L.kv32;
+    A.silu_tab = L.silu_tab;
+}
+
+// the input that prologue pro reads must be there
+inline bool mv_inputs_set(const MvLaunch & L, int pro) {
+    switch (pro) {
+        case PRO_NORM: return L.x && L.g;
+        case PRO_ACTF: return L.x != nullptr;
+        case PRO_ACTQ: return L.xq.qs && L.xq.d && (L.w.qtype != Q4_1 || L.xq.m);
+    }
+    return false;
+}
+
+// ---- f32 -> activation table prologue.  A work unit is 8 consecutive elements; thread t of NT
+// holds units k * NT + t (k < UM) in registers; the 4 units of a block are a lane quad
+// (nunits % 4 == 0, NT % 4 == 0).
+
+__device__ __forceinline__ void unit_vals(const float4 & a, const float4 & b, float (&v)[8]) {
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+}
+
+// the unit loads (x, and g for PRO_NORM), clamped to the last unit: every thread issues them all
+template <int NT, int PRO, int UM, int GM>
+__device__ __forceinline__ void pro_load_units(const float * x, const float * g, int nunits, int t,
+                                               float4 (&xv)[UM][2], float4 (&gv)[GM][2]) {
+#pragma unroll
+    for (int k = 0; k < UM; ++k) {
+        const int un = min(k * NT + t, nunits - 1);
+        const float4 * xp = (const float4 *) (x + (size_t) un * 8);
+        xv[k][0] = xp[0]; xv[k][1] = xp[1];
+        if constexpr (PRO == PRO_NORM) {
+            const float4 * gp = (const float4 *) (g + (size_t) un * 8);
+            gv[k][0] = gp[0]; gv[k][1] = gp[1];
+        }
+    }
+}
+
+// ggml_compute_forward_rms_norm_f32's sum (ggml.c:6058-6070): float squares carried in double,
+// in element order (RMSNorm order)
+__device__ __forceinline__ void sumsq4(double & acc, const float4 & v) {
+    const float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { const float sq = e[q] * e[q]; acc += (double) sq; }
+}
+template <int NT, int UM>
+__device__ __forceinline__ double pro_sumsq_units(const float4 (&xv)[UM][2], int nunits, int t) {
+    double acc = 0.0;
+#pragma unroll
+    for (int k = 0; k < UM; ++k)
+        if (k * NT + t < nunits) { sumsq4(acc, xv[k][0]); sumsq4(acc, xv[k][1]); }
+    return acc;
+}
+
+// PRO_NORM: a unit of rms_norm(x) * g
+template <int PRO>
+__device__ __forceinline__ void pro_norm_unit(float (&v)[8], const float4 & ga, const float4 & gb, float scale) {
+    if constexpr (PRO == PRO_NORM) {
+        float gg[8];
+        unit_vals(ga, gb, gg);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float yn = v[e] * scale;      // ggml_vec_scale_f32 (ggml.c:6076)
+            v[e] = gg[e] * yn;                  // ggml_mul(repeat(g), cur) (llama.cpp:984)
+        }
+    }
+}
+
+// quantize_row_q4_0 of the block a lane quad holds, unit un = this lane's 8 elements, into the
+// table (act_store; the quad's first lane also writes d)
+__device__ __forceinline__ void q40_unit_store(const float (&v)[8], int un, bool live, uint32_t * act, float * dxp) {
+    float amax = 0.0f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const float a = fabsf(v[e]);
+        amax = a > amax ? a : amax;
+    }
+    // block amax (ggml.c:636-649)
+    const float o0 = quad_bcast<0>(amax), o1 = quad_bcast<1>(amax);
+    const float o2 = quad_bcast<2>(amax), o3 = quad_bcast<3>(amax);
+    const float m01 = o1 > o0 ? o1 : o0, m23 = o3 > o2 ? o3 : o2;
+    amax = m23 > m01 ? m23 : m01;
+    const float d = amax / 7.0f;                              // ggml.c:651
+    const float id = (amax != 0.0f) ? 7.0f / amax : 0.0f;     // ggml.c:653
+    const uint32_t w = q40_pack8(v, id);
+    if (live) act_store(act, dxp, un >> 2, un & 3, w, d, (un & 3) == 0);
+}
+
+// quantize_row_q4_1 of the block a lane quad holds (q41_quad), its 4 qs words gathered into
+// every lane; the quad's first lane stores the block (act41_store)
+template <typename YS>
+__device__ __forceinline__ void q41_unit_store(const float (&v)[8], int un, bool live, uint32_t * act, float * dyv,
+                                               float * myv, YS * ysum) {
+    float d, m;
+    uint32_t qw;
+    q41_quad(v, d, m, qw);
+    uint32_t qs[4];
+    qs[0] = __builtin_bit_cast(uint32_t, quad_bcast<0>(__builtin_bit_cast(float, qw)));
+    qs[1] = __builtin_bit_cast(uint32_t, quad_bcast<1>(__builtin_bit_cast(float, qw)));
+    qs[2] = __builtin_bit_cast(uint32_t, quad_bcast<2>(__builtin_bit_cast(float, qw)));
+    qs[3] = __builtin_bit_cast(uint32_t, quad_bcast<3>(__builtin_bit_cast(float, qw)));
+    if (live && (un & 3) == 0) act41_store(act, dyv, myv, ysum, un >> 2, qs, d, m);
+}
+
+// the register-held units of thread t: scale * g (PRO_NORM), quantize, store
+template <int NT, int PRO, int UM, int GM>
+__device__ __forceinline__ void pro_q40_units(const float4 (&xv)[UM][2], const float4 (&gv)[GM][2], float scale,
+                                              int nunits, int t, uint32_t * act, float * dxp) {
+#pragma unroll
+    for (int k = 0; k < UM; ++k) {
+        if (k * NT >= nunits) break;
+        const int un = k * NT + t;
+        constexpr int GK = PRO == PRO_NORM ? 1 : 0;
+        float v[8];
+        unit_vals(xv[k][0], xv[k][1], v);
+        pro_norm_unit<PRO>(v, gv[GK * k][0], gv[GK * k][1], scale);
+        q40_unit_store(v, un, un < nunits, act, dxp);
+    }
+}
+template <int NT, int PRO, int UM, int GM, typename YS>
+__device__ __forceinline__ void pro_q41_units(const float4 (&xv)[UM][2], const float4 (&gv)[GM][2], float scale,
+                                              int nunits, int t, uint32_t * act, float * dyv, float * myv, YS * ysum) {
+#pragma unroll
+    for (int k = 0; k < UM; ++k) {
+        if (k * NT >= nunits) break;
+        const int un = k * NT + t;
+        constexpr int GK = PRO == PRO_NORM ? 1 : 0;
+        float v[8];
+        unit_vals(xv[k][0], xv[k][1], v);
+        pro_norm_unit<PRO>(v, gv[GK * k][0], gv[GK * k][1], scale);
+        q41_unit_store(v, un, un < nunits, act, dyv, myv, ysum);
+    }
+}
+
+// PRO_ACTQ: a pre-quantized block b into the table
+__device__ __forceinline__ void q40_block_store(uint32_t * act, float * dxp, int b, const uint4 & qs, float d) {
+    act_store(act, dxp, b, 0, qs.x, d, true);
+    act_store(act, dxp, b, 1, qs.y, 0.0f, false);
+    act_store(act, dxp, b, 2, qs.z, 0.0f, false);
+    act_store(act, dxp, b, 3, qs.w, 0.0f, false);
+}
+template <typename YS>
+__device__ __forceinline__ void q41_block_store(uint32_t * act, float * dyv, float * myv, YS * ysum, int b,
+                                                const uint4 & q, float d, float m) {
+    const uint32_t qs[4] = {q.x, q.y, q.z, q.w};
+    act41_store(act, dyv, myv, ysum, b, qs, d, m);
+}
+
+// ---- epilogues
+
+// RoPE mode 0 of one element (ggml_compute_forward_rope_f32, ggml.c:7209-7223): res is element
+// i0 of its head, other its partner i0 ^ 1, cs the pair's {cos, sin}
+__device__ __forceinline__ float rope_rot(float res, float other, int i0, float2 cs) {
+    if ((i0 & 1) == 0) { const float a = res * cs.x, b = other * cs.y; return a - b; }
+    const float a = other * cs.y, b = res * cs.x;
+    return a + b;
+}
+
+// silu(w1 x) * (w3 x): ggml_vec_silu_f32's f16 table (ggml.c:2495), then ggml_mul (llama.cpp:1096)
+__device__ __forceinline__ float silu_mul(float a1, float a3, const uint16_t * silu_tab) {
+    const float sl = f16_to_f32(silu_tab[f32_to_f16(a1)]);
+    return sl * a3;
+}
+
+// QKV epilogue of the single-token matvecs, per output row (lane row r of an 8-row group, chain
+// lane j; rows e and e^1 are lanes l and l^8) with the lane's RoPE pair loaded
+// (cs: rope[pos * hd / 2 + (e % hd) / 2]): RoPE on q and k, then the q row / K-cache row /
+// V-cache column stores (llama.cpp:996-1008)
+__device__ __forceinline__ void qkv_epilogue_cs(float res, int row, int j, int E, int hd, int pos, float2 cs,
+                                                uint16_t * q16, uint16_t * kc, uint16_t * vc, int n_ctx, int kv32) {
     const int which = row / E;              // 0 q, 1 k, 2 v (uniform per wave: E % 8 == 0)
     const int e = row - which * E;
     const float other = __shfl_xor(res, 8);   // row e^1 lives in lanes of row r^1
     float out = res;
-    if (which < 2) {
-        const int i0 = e % hd;
-        const float2 cs = rope[(size_t) pos * (hd / 2) + (i0 >> 1)];
-        if ((i0 & 1) == 0) { const float a = res * cs.x, b = other * cs.y; out = a - b; }
-        else               { const float a = other * cs.y, b = res * cs.x; out = a + b; }
-    }
+    if (which < 2) out = rope_rot(res, other, e % hd, cs);
     if (j == 0) {
         if (which == 0)      kv_store(q16, e, out, kv32);
         else if (which == 1) kv_store(kc, (size_t) pos * E + e, out, kv32);
@@ -237,22 +435,78 @@ __device__ __forceinline__ void qkv_epilogue(float res, int row, int j, int E, i
     }
 }
 
-// qkv_epilogue with the lane's RoPE pair already loaded (cs: rope[pos * hd / 2 + (e % hd) / 2])
-__device__ __forceinline__ void qkv_epilogue_cs(float res, int row, int j, int E, int hd, int pos, float2 cs,
-                                                uint16_t * q16, uint16_t * kc, uint16_t * vc, int n_ctx, int kv32) {
-    const int which = row / E;
-    const int e = row - which * E;
-    const float other = __shfl_xor(res, 8);
-    float out = res;
-    if (which < 2) {
-        const int i0 = e % hd;
-        if ((i0 & 1) == 0) { const float a = res * cs.x, b = other * cs.y; out = a - b; }
-        else               { const float a = other * cs.y, b = res * cs.x; out = a + b; }
+// The single-token epilogue of row grp * 8 + r (k_mv_cu, k_mv_cu41, k_matvec_f16).  mv_pre_epi
+// loads its memory operand -- the lane's RoPE pair (pos0 = n_past), or the residual term;
+// the CU kernels issue it before the row group's chunk loop: loaded in the epilogue it was a
+// full memory round trip in every wave's tail (QKV 7.60 -> 7.45, Wo 4.41 -> 4.25, W2 7.33 ->
+// 7.26 us; profiles/r06/decode_ab/epilogue_summary.txt)
+struct EpiPre { float2 cs; float rv; };
+template <int EPI>
+__device__ __forceinline__ EpiPre mv_pre_epi(const MvArgs & P, int row, int pos0) {
+    EpiPre e{make_float2(0.0f, 0.0f), 0.0f};
+    if constexpr (EPI == EPI_QKV) {
+        const int i0 = (row - (row / P.n_embd) * P.n_embd) % P.head_dim;   // V rows: an unused pair
+        e.cs = P.rope[(size_t) pos0 * (P.head_dim / 2) + (i0 >> 1)];
+    } else if constexpr (EPI == EPI_RESID) {
+        e.rv = P.y[row];
     }
-    if (j == 0) {
-        if (which == 0)      kv_store(q16, e, out, kv32);
-        else if (which == 1) kv_store(kc, (size_t) pos * E + e, out, kv32);
-        else                 kv_store(vc, (size_t) e * n_ctx + pos, out, kv32);
+    return e;
+}
+// live: the row exists (the last group of an M % 8 != 0 f16 matrix, EPI_STORE only)
+template <int EPI>
+__device__ __forceinline__ void mv_epilogue(const MvArgs & P, int grp, int r, int j, float res, int pos0,
+                                            const EpiPre & pe, bool live = true) {
+    const int row = grp * 8 + r;
+    if constexpr (EPI == EPI_STORE) {
+        if (j == 0 && live) P.y[row] = res;
+    } else if constexpr (EPI == EPI_RESID) {
+        if (j == 0 && live) P.y[row] = res + pe.rv;     // ggml_add(cur, inpSA) (llama.cpp:1071,1103)
+    } else if constexpr (EPI == EPI_QKV) {
+        qkv_epilogue_cs(res, row, j, P.n_embd, P.head_dim, pos0, pe.cs, P.q16, P.kc, P.vc, P.n_ctx, P.kv32);
+    } else if constexpr (EPI == EPI_SWIGLU_F32) {
+        // fused W1|W3 image interleaved per 4 rows: rows 0-3 of the group are
+        // w1 rows 4grp..4grp+3, rows 4-7 the w3 rows (llama.cpp:1085-1096)
+        const float a3 = __shfl_xor(res, 32);
+        if (r < 4 && j == 0) P.u[grp * 4 + r] = silu_mul(res, a3, P.silu_tab);
+    }
+}
+
+// The STORE / RESID / QKV epilogue of the generic kernels: results res[tt] of row `row` for
+// tokens t0 .. t0 + nt - 1 (chain lane j; y is [N][M])
+template <int T, int EPI>
+__device__ __forceinline__ void mv_epilogue_rows(const MvArgs & P, const float (&res)[T], int row, int j, int M, int t0,
+                                                 int nt) {
+    if constexpr (EPI == EPI_STORE) {
+#pragma unroll
+        for (int tt = 0; tt < T; ++tt)
+            if (tt < nt && j == 0) P.y[(size_t) (t0 + tt) * M + row] = res[tt];
+    } else if constexpr (EPI == EPI_RESID) {
+#pragma unroll
+        for (int tt = 0; tt < T; ++tt)
+            if (tt < nt && j == 0) {
+                float * yp = P.y + (size_t) (t0 + tt) * M + row;
+                *yp = res[tt] + *yp;                 // the residual add, as mv_epilogue
+            }
+    } else if constexpr (EPI == EPI_QKV) {
+        const int E = P.n_embd, hd = P.head_dim;
+        const int which = row / E;          // 0 q, 1 k, 2 v (uniform per wave: E % 8 == 0)
+        const int e = row - which * E;
+        const int n_past = P.sp->n_past;
+#pragma unroll
+        for (int tt = 0; tt < T; ++tt) {
+            const float other = __shfl_xor(res[tt], 8);   // row e^1 lives in lanes of row r^1
+            if (tt < nt && j == 0) {
+                const int pos = n_past + t0 + tt;
+                if (which < 2) {
+                    const int i0 = e % hd;
+                    const float out = rope_rot(res[tt], other, i0, P.rope[(size_t) pos * (hd / 2) + (i0 >> 1)]);
+                    if (which == 0) kv_store(P.q16, (size_t) (t0 + tt) * E + e, out, P.kv32);
+                    else            kv_store(P.kc, (size_t) pos * E + e, out, P.kv32);
+                } else {
+                    kv_store(P.vc, (size_t) e * P.n_ctx + pos, res[tt], P.kv32);
+                }
+            }
+        }
     }
 }
 
@@ -321,7 +575,7 @@ __device__ __forceinline__ void mm_epi_store(const float (&res)[16], float * y, 
 #pragma unroll
                 for (int p = 0; p < 4; ++p) {
                     const float sl = f16_to_f32(silu_tab[f32_to_f16(res[4 * q + p])]);  // ggml.c:2495
-                    uu[p] = sl * o[4 * q + p];                                          // llama.cpp:1096
+                    uu[p] = sl * o[4 * q + p];                                          // ggml_mul
                 }
                 const int row = m0 + 32 * w + 8 * q;
                 *(float4 *) (y + (size_t) n * ldy + row / 2) = make_float4(uu[0], uu[1], uu[2], uu[3]);
@@ -336,7 +590,7 @@ __device__ __forceinline__ void mm_epi_store(const float (&res)[16], float * y, 
             for (int q = 0; q < 4; ++q) {
                 float4 * yp = (float4 *) (y + (size_t) n * ldy + m0 + 32 * w + 8 * q + 4 * h);
                 if constexpr (EPI == EPI_RESID) {
-                    const float4 r = *yp;                 // ggml_add(cur, inpSA) (llama.cpp:1071,1103)
+                    const float4 r = *yp;                 // the residual add, as mv_epilogue
                     *yp = make_float4(res[4 * q] + r.x, res[4 * q + 1] + r.y, res[4 * q + 2] + r.z, res[4 * q + 3] + r.w);
                 } else {
                     *yp = make_float4(res[4 * q], res[4 * q + 1], res[4 * q + 2], res[4 * q + 3]);

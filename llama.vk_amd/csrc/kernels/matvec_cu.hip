@@ -37,23 +37,26 @@ __device__ unsigned long long g_trace[256 * 16 * 64];
 #define LVK_T(ev) do { } while (0)
 #endif
 
-struct CuParams {
+// (the images lead the block: the kernel's first scalar loads fetch what the row-group split and
+// the weight addresses need)
+struct CuImages {
     const uint4 * nib;
     const float4 * scl;
     int G;                      // row groups (M / 8)
-    const float * x;            // PRO_NORM / PRO_ACTF: f32 input [K]
-    const float * g;            // PRO_NORM: norm weight [K]
-    ActQ xq;                    // PRO_ACTQ: quantized input
-    const StepParams * sp;
-    float * y;                  // EPI_STORE / EPI_RESID
-    float * u;                  // EPI_SWIGLU_F32: silu(w1 x) * (w3 x) [M/2]
-    uint16_t * q16;
-    uint16_t * kc;
-    uint16_t * vc;
-    const float2 * rope;
-    int n_embd, head_dim, n_ctx;
-    int kv32;                   // f32 KV cache and queries (f16_kv = false)
-    const uint16_t * silu_tab;
+};
+struct CuParams : CuImages, MvArgs {};
+
+// order of the prologue and the first weight loads (k_mv_cu PF; the values are what the sweep
+// build's LVK_MV_PF takes)
+enum PfOrder : int {
+    PF_ISSUE_FIRST = 0,     // the inputs, then the weights are issued, then the activation table is
+                            // built as soon as the inputs land (the weights stay in flight)
+    PF_INPUTS_LAND = 1,     // the inputs land, then the weights are issued, then the table is built
+    PF_TABLE_FIRST = 2,     // the inputs land and the table is built, then the weights are issued
+    PF_SPLIT = 5,           // the inputs land, chunk 0 is issued, the table is built, chunks 1..D-1
+                            // go out after the workgroup barrier (the barriers wait for the slowest
+                            // wave's issue, which the memory system throttles to the return rate
+                            // once the CU's queue is full)
 };
 
 // per-wave block-scale table s = dw * dx in LDS (two buffers, 8 rows x 32 blocks): the row
@@ -92,16 +95,7 @@ __device__ __forceinline__ void mv_cu_run(const CuParams & P, const int bid, con
             constexpr int UMP = (nunits + PT_ - 1) / PT_;
             float4 xv[UMP][2];
             float4 gv[PRO == PRO_NORM ? UMP : 1][2];
-#pragma unroll
-            for (int k = 0; k < UMP; ++k) {
-                const int un = min(k * PT_ + pt, nunits - 1);
-                const float4 * xp = (const float4 *) (P.x + (size_t) un * 8);
-                xv[k][0] = xp[0]; xv[k][1] = xp[1];
-                if constexpr (PRO == PRO_NORM) {
-                    const float4 * gp = (const float4 *) (P.g + (size_t) un * 8);
-                    gv[k][0] = gp[0]; gv[k][1] = gp[1];
-                }
-            }
+            pro_load_units<PT_, PRO>(P.x, P.g, nunits, pt, xv, gv);
             constexpr int XPL = PRO == PRO_NORM ? KT / 4 / 64 : 1;
             float4 xs[XPL];
             if constexpr (PRO == PRO_NORM) {
@@ -112,66 +106,26 @@ __device__ __forceinline__ void mv_cu_run(const CuParams & P, const int bid, con
             __builtin_amdgcn_s_barrier();
             float scale = 1.0f;
             if constexpr (PRO == PRO_NORM) {
-                // ggml_compute_forward_rms_norm_f32 (ggml.c:6058-6076): every
-                // prologue wave sums all K squares itself (lane-strided, then a
+                // every prologue wave sums all K squares itself (lane-strided, then a
                 // butterfly that leaves the same double in every lane), so no
-                // cross-wave reduction is needed.  Terms are float squares
-                // carried in double (RMSNorm order).
+                // cross-wave reduction is needed
                 double acc = 0.0;
 #pragma unroll
-                for (int i = 0; i < XPL; ++i) {
-                    const float e[4] = {xs[i].x, xs[i].y, xs[i].z, xs[i].w};
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) { const float sq = e[q] * e[q]; acc += (double) sq; }
-                }
+                for (int i = 0; i < XPL; ++i) sumsq4(acc, xs[i]);
                 LVK_T(56);
                 acc = warp_sum_d(acc);
                 const float mean = rms_mean_wave(acc, P.x, KT);
                 scale = 1.0f / sqrtf(mean + 1e-6f);
                 LVK_T(57);
             }
-#pragma unroll
-            for (int k = 0; k < UMP; ++k) {
-                if (k * PT_ >= nunits) break;
-                const int un = k * PT_ + pt;
-                float v[8] = {xv[k][0].x, xv[k][0].y, xv[k][0].z, xv[k][0].w,
-                              xv[k][1].x, xv[k][1].y, xv[k][1].z, xv[k][1].w};
-                float amax = 0.0f;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    if constexpr (PRO == PRO_NORM) {
-                        const float gg[8] = {gv[k][0].x, gv[k][0].y, gv[k][0].z, gv[k][0].w,
-                                             gv[k][1].x, gv[k][1].y, gv[k][1].z, gv[k][1].w};
-                        const float yn = v[e] * scale;      // ggml_vec_scale_f32 (ggml.c:6076)
-                        v[e] = gg[e] * yn;                  // ggml_mul(repeat(g), cur) (llama.cpp:984)
-                    }
-                    const float a = fabsf(v[e]);
-                    amax = a > amax ? a : amax;
-                }
-                // the 4 units of a block are a lane quad: block amax (ggml.c:636-649)
-                const float o0 = quad_bcast<0>(amax), o1 = quad_bcast<1>(amax);
-                const float o2 = quad_bcast<2>(amax), o3 = quad_bcast<3>(amax);
-                const float m01 = o1 > o0 ? o1 : o0, m23 = o3 > o2 ? o3 : o2;
-                amax = m23 > m01 ? m23 : m01;
-                const float d = amax / 7.0f;                              // ggml.c:651
-                const float id = (amax != 0.0f) ? 7.0f / amax : 0.0f;     // ggml.c:653
-                const uint32_t w = q40_pack8(v, id);
-                if (un < nunits) act_store(act, dxp, un >> 2, un & 3, w, d, (un & 3) == 0);
-            }
+            pro_q40_units<PT_, PRO>(xv, gv, scale, nunits, pt, act, dxp);
         } else {
             __builtin_amdgcn_s_barrier();       // barrier A (see above)
             constexpr int UMP = (nb + PT_ - 1) / PT_;
 #pragma unroll
             for (int k = 0; k < UMP; ++k) {
                 const int b = k * PT_ + pt;
-                if (b < nb) {
-                    const uint4 qs = P.xq.qs[b];
-                    const float d = P.xq.d[b];
-                    act_store(act, dxp, b, 0, qs.x, d, true);
-                    act_store(act, dxp, b, 1, qs.y, 0.0f, false);
-                    act_store(act, dxp, b, 2, qs.z, 0.0f, false);
-                    act_store(act, dxp, b, 3, qs.w, 0.0f, false);
-                }
+                if (b < nb) q40_block_store(act, dxp, b, P.xq.qs[b], P.xq.d[b]);
             }
         }
         LVK_T(2);
@@ -189,7 +143,7 @@ __device__ __forceinline__ void mv_cu_run(const CuParams & P, const int bid, con
     int gc = min(g0 + wave, P.G - 1);
     // the QKV epilogue's position, loaded here ahead of the prologue inputs (vmcnt retires in
     // order: the inputs' wait covers it), so that the RoPE pair can be loaded at a row group's
-    // start (pre_epi below).  An atomic load: a plain one is sunk to its use; a scalar one sinks
+    // start (mv_pre_epi).  An atomic load: a plain one is sunk to its use; a scalar one sinks
     // too and then holds up the prologue's first barrier, whose lgkmcnt wait covers it.
     [[maybe_unused]] int pos0 = 0;
     if constexpr (EPI == EPI_QKV)
@@ -207,16 +161,7 @@ __device__ __forceinline__ void mv_cu_run(const CuParams & P, const int bid, con
     float dv[UM];
     if constexpr (NP == 0) {
         if constexpr (FPRO) {
-#pragma unroll
-            for (int k = 0; k < UM; ++k) {
-                const int un = min(k * NT + tid, nunits - 1);
-                const float4 * xp = (const float4 *) (P.x + (size_t) un * 8);
-                xv[k][0] = xp[0]; xv[k][1] = xp[1];
-                if constexpr (PRO == PRO_NORM) {
-                    const float4 * gp = (const float4 *) (P.g + (size_t) un * 8);
-                    gv[k][0] = gp[0]; gv[k][1] = gp[1];
-                }
-            }
+            pro_load_units<NT, PRO>(P.x, P.g, nunits, tid, xv, gv);
         } else {
 #pragma unroll
             for (int k = 0; k < UM; ++k) {
@@ -261,31 +206,23 @@ __device__ __forceinline__ void mv_cu_run(const CuParams & P, const int bid, con
             W[slot][sb] = ld_nt((const uint4 *) ((const char *) (nb_ + sb * 64) + loff));               \
         __builtin_amdgcn_sched_barrier(0);                                                              \
     } while (0)
-    // Order of the prologue and the first weight loads (PF):
-    //   0: the inputs, then the weights are issued, then the activation table is built as
-    //      soon as the inputs land (the weights stay in flight);
-    //   1: the inputs land, then the weights are issued, then the table is built;
-    //   2: the inputs land and the table is built, then the weights are issued;
-    //   3: as 2, but the weights are issued after the workgroup barrier;
-    //   4: as 0, but only chunk 0 goes out before the table, chunks 1..D-1 after the barrier
-    //      (the barriers wait for the slowest wave's issue, which the memory system throttles
-    //      to the return rate once the CU's queue is full);
-    //   5: as 4, but the inputs land before chunk 0 is issued.
+    // Order of the prologue and the first weight loads: PF (PfOrder).
     // A CU's texture unit takes a 1 KiB wave load in ~16 cycles: issuing 80-160 KiB of
-    // weights keeps every wave of the CU in its issue for 1.3-4k cycles, so with 0 or 1 the
-    // table (and the first chain) waits for the wave's own share of the burst to be issued.
-    constexpr bool SPLIT = PF == 4 || PF == 5;
-    if constexpr (PF != 0 && PF != 4) launder_inputs();
+    // weights keeps every wave of the CU in its issue for 1.3-4k cycles, so with
+    // PF_ISSUE_FIRST or PF_INPUTS_LAND the table (and the first chain) waits for the wave's own
+    // share of the burst to be issued.
+    static_assert(PF == PF_ISSUE_FIRST || PF == PF_INPUTS_LAND || PF == PF_TABLE_FIRST || PF == PF_SPLIT, "PfOrder");
+    if constexpr (PF != PF_ISSUE_FIRST) launder_inputs();
     // prologue waves (NP > 0): the weight burst goes out behind their inputs (barrier A)
     if constexpr (NP > 0) __builtin_amdgcn_s_barrier();
     LVK_T(58);
-    if constexpr (PF <= 1) {
+    if constexpr (PF == PF_ISSUE_FIRST || PF == PF_INPUTS_LAND) {
 #pragma unroll
         for (int d = 0; d < D; ++d) LVK_ISSUE(d, gc, d);
-    } else if constexpr (SPLIT) {
+    } else if constexpr (PF == PF_SPLIT) {
         LVK_ISSUE(0, gc, 0);
     }
-    if constexpr (PF == 0 || PF == 4) launder_inputs();
+    if constexpr (PF == PF_ISSUE_FIRST) launder_inputs();
     LVK_T(59);
 
     if constexpr (NP == 0) {
@@ -293,19 +230,9 @@ __device__ __forceinline__ void mv_cu_run(const CuParams & P, const int bid, con
         if constexpr (FPRO) {
             float scale = 1.0f;
             if constexpr (PRO == PRO_NORM) {
-                // ggml_compute_forward_rms_norm_f32 (ggml.c:6058-6076): float
-                // squares summed in double; per-thread units, a DPP wave tree,
-                // then the NW wave sums in order (RMSNorm order)
-                double acc = 0.0;
-#pragma unroll
-                for (int k = 0; k < UM; ++k) {
-                    if (k * NT + tid < nunits) {
-                        const float e[8] = {xv[k][0].x, xv[k][0].y, xv[k][0].z, xv[k][0].w,
-                                            xv[k][1].x, xv[k][1].y, xv[k][1].z, xv[k][1].w};
-#pragma unroll
-                        for (int q = 0; q < 8; ++q) { const float sq = e[q] * e[q]; acc += (double) sq; }
-                    }
-                }
+                // per-thread units, a DPP wave tree, then the NW wave sums in order
+                // (RMSNorm order)
+                double acc = pro_sumsq_units<NT>(xv, nunits, tid);
                 acc = wave_sum_d(acc);
                 if (lane == 0) red[wave] = acc;
                 __syncthreads();
@@ -315,47 +242,16 @@ __device__ __forceinline__ void mv_cu_run(const CuParams & P, const int bid, con
                 const float mean = rms_mean_wave(sum, P.x, KT);
                 scale = 1.0f / sqrtf(mean + 1e-6f);
             }
-#pragma unroll
-            for (int k = 0; k < UM; ++k) {
-                if (k * NT >= nunits) break;
-                const int un = k * NT + tid;
-                float v[8] = {xv[k][0].x, xv[k][0].y, xv[k][0].z, xv[k][0].w,
-                              xv[k][1].x, xv[k][1].y, xv[k][1].z, xv[k][1].w};
-                float amax = 0.0f;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    if constexpr (PRO == PRO_NORM) {
-                        const float gg[8] = {gv[k][0].x, gv[k][0].y, gv[k][0].z, gv[k][0].w,
-                                             gv[k][1].x, gv[k][1].y, gv[k][1].z, gv[k][1].w};
-                        const float yn = v[e] * scale;      // ggml_vec_scale_f32 (ggml.c:6076)
-                        v[e] = gg[e] * yn;                  // ggml_mul(repeat(g), cur) (llama.cpp:984)
-                    }
-                    const float a = fabsf(v[e]);
-                    amax = a > amax ? a : amax;
-                }
-                const float o0 = quad_bcast<0>(amax), o1 = quad_bcast<1>(amax);
-                const float o2 = quad_bcast<2>(amax), o3 = quad_bcast<3>(amax);
-                const float m01 = o1 > o0 ? o1 : o0, m23 = o3 > o2 ? o3 : o2;
-                amax = m23 > m01 ? m23 : m01;
-                const float d = amax / 7.0f;                              // ggml.c:651
-                const float id = (amax != 0.0f) ? 7.0f / amax : 0.0f;     // ggml.c:653
-                const uint32_t w = q40_pack8(v, id);
-                if (un < nunits) act_store(act, dxp, un >> 2, un & 3, w, d, (un & 3) == 0);
-            }
+            pro_q40_units<NT, PRO>(xv, gv, scale, nunits, tid, act, dxp);
         } else {
 #pragma unroll
             for (int k = 0; k < UM; ++k) {
                 const int b = k * NT + tid;
-                if (b < nb) {
-                    act_store(act, dxp, b, 0, qv[k].x, dv[k], true);
-                    act_store(act, dxp, b, 1, qv[k].y, 0.0f, false);
-                    act_store(act, dxp, b, 2, qv[k].z, 0.0f, false);
-                    act_store(act, dxp, b, 3, qv[k].w, 0.0f, false);
-                }
+                if (b < nb) q40_block_store(act, dxp, b, qv[k], dv[k]);
             }
         }
     }
-    if constexpr (PF == 2) {
+    if constexpr (PF == PF_TABLE_FIRST) {
 #pragma unroll
         for (int d = 0; d < D; ++d) LVK_ISSUE(d, gc, d);
     }
@@ -363,12 +259,7 @@ __device__ __forceinline__ void mv_cu_run(const CuParams & P, const int bid, con
     __syncthreads();            // activation table ready
     LVK_T(2);
     if (NP == 0 && ng == 0) return;
-    if constexpr (PF == 3) {
-        // 3: the table first, then every wave issues its own weights and starts its chain
-        // as soon as they land (no workgroup barrier behind the issue)
-#pragma unroll
-        for (int d = 0; d < D; ++d) LVK_ISSUE(d, gc, d);
-    } else if constexpr (SPLIT) {
+    if constexpr (PF == PF_SPLIT) {
 #pragma unroll
         for (int d = 1; d < D; ++d) LVK_ISSUE(d, gc, d);
     }
@@ -386,18 +277,8 @@ __device__ __forceinline__ void mv_cu_run(const CuParams & P, const int bid, con
         sv.x = Sv.x * dx.x; sv.y = Sv.y * dx.y; sv.z = Sv.z * dx.z; sv.w = Sv.w * dx.w;
         *(float4 *) (sw + buf * SPL + r * SRS + j * 4) = sv;
     };
-#ifndef LVK_PROBE_EXP
-#define LVK_PROBE_EXP 0
-#endif
-    // dev probe builds only (tools/probe mv_probe_xN): cost of the chain's parts.  1: four
-    // independent accumulators per lane instead of one serial chain; 2: no int -> float
-    // conversion (bit cast); 4: the scale products taken from registers, not the LDS table.
-    // None of these is bit-exact; the product build has LVK_PROBE_EXP = 0.
-    constexpr bool X_IND = (LVK_PROBE_EXP & 1) != 0, X_NOCVT = (LVK_PROBE_EXP & 2) != 0;
-    constexpr bool X_NOSA = (LVK_PROBE_EXP & 4) != 0;
     auto body = [&](auto has_next, int grp, int gnext) __attribute__((always_inline)) {
-        float acc = 0.0f, acc1 = 0.0f, acc2 = 0.0f, acc3 = 0.0f;
-        auto cv = [](int p) __attribute__((always_inline)) { return X_NOCVT ? __int_as_float(p) : (float) p; };
+        float acc = 0.0f;
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             const int slot = c % D;
@@ -417,7 +298,7 @@ __device__ __forceinline__ void mv_cu_run(const CuParams & P, const int bid, con
             float sa[8][4];
 #pragma unroll
             for (int jj = 0; jj < 8; ++jj) {
-                const float4 v = X_NOSA ? S[slot] : *(const float4 *) (sl + r * SRS + jj * 4);
+                const float4 v = *(const float4 *) (sl + r * SRS + jj * 4);
                 sa[jj][0] = v.x; sa[jj][1] = v.y; sa[jj][2] = v.z; sa[jj][3] = v.w;
             }
 #pragma unroll
@@ -432,13 +313,10 @@ __device__ __forceinline__ void mv_cu_run(const CuParams & P, const int bid, con
                         const int p1 = dot8(wd[2 * pp], a.y);
                         const int p2 = dot8(wd[2 * pp + 1], a.z);
                         const int p3 = dot8(wd[2 * pp + 1], a.w);
-                        acc = __builtin_fmaf(sa[(bi + 0) & 7][(bi + 0) >> 3], cv(p0), acc);
-                        float & a1 = X_IND ? acc1 : acc;
-                        a1 = __builtin_fmaf(sa[(bi + 1) & 7][(bi + 1) >> 3], cv(p1), a1);
-                        float & a2 = X_IND ? acc2 : acc;
-                        a2 = __builtin_fmaf(sa[(bi + 2) & 7][(bi + 2) >> 3], cv(p2), a2);
-                        float & a3 = X_IND ? acc3 : acc;
-                        a3 = __builtin_fmaf(sa[(bi + 3) & 7][(bi + 3) >> 3], cv(p3), a3);
+                        acc = __builtin_fmaf(sa[(bi + 0) & 7][(bi + 0) >> 3], (float) p0, acc);
+                        acc = __builtin_fmaf(sa[(bi + 1) & 7][(bi + 1) >> 3], (float) p1, acc);
+                        acc = __builtin_fmaf(sa[(bi + 2) & 7][(bi + 2) >> 3], (float) p2, acc);
+                        acc = __builtin_fmaf(sa[(bi + 3) & 7][(bi + 3) >> 3], (float) p3, acc);
                     }
                 }
             }
@@ -454,63 +332,26 @@ __device__ __forceinline__ void mv_cu_run(const CuParams & P, const int bid, con
             // keep chunks in program order: the chain value is pinned here, so
             // chunk c's arithmetic cannot sink below chunk c+1's reads
             asm volatile("" : "+v"(acc));
-            if constexpr (X_IND) asm volatile("" : "+v"(acc1), "+v"(acc2), "+v"(acc3));
             LVK_T(tq); ++tq;
             __builtin_amdgcn_sched_barrier(0);
         }
-        if constexpr (X_IND) acc = (acc + acc1) + (acc2 + acc3);
         return octet_reduce(acc);
-    };
-
-    // the epilogue's memory operand of a row group -- the lane's RoPE pair, or the residual term --
-    // issued before the group's chunk loop: loaded in the epilogue it was a full memory round
-    // trip in every wave's tail (QKV 7.60 -> 7.45, Wo 4.41 -> 4.25, W2 7.33 -> 7.26 us;
-    // profiles/r06/decode_ab/epilogue_summary.txt)
-    struct EpiPre { float2 cs; float rv; };
-    auto pre_epi = [&](int grp) __attribute__((always_inline)) {
-        EpiPre e{make_float2(0.0f, 0.0f), 0.0f};
-        if constexpr (EPI == EPI_QKV) {
-            const int row = grp * 8 + r;
-            const int i0 = (row - (row / P.n_embd) * P.n_embd) % P.head_dim;   // V rows: an unused pair
-            e.cs = P.rope[(size_t) pos0 * (P.head_dim / 2) + (i0 >> 1)];
-        } else if constexpr (EPI == EPI_RESID) {
-            e.rv = P.y[grp * 8 + r];
-        }
-        return e;
-    };
-    auto epilogue = [&](int grp, float res, const EpiPre & pe) __attribute__((always_inline)) {
-        const int row = grp * 8 + r;
-        if constexpr (EPI == EPI_STORE) {
-            if (j == 0) P.y[row] = res;
-        } else if constexpr (EPI == EPI_RESID) {
-            // ggml_add(cur, inpSA) (llama.cpp:1071,1103)
-            if (j == 0) P.y[row] = res + pe.rv;
-        } else if constexpr (EPI == EPI_QKV) {
-            qkv_epilogue_cs(res, row, j, P.n_embd, P.head_dim, pos0, pe.cs, P.q16, P.kc, P.vc, P.n_ctx, P.kv32);
-        } else if constexpr (EPI == EPI_SWIGLU_F32) {
-            // fused W1|W3 image interleaved per 4 rows: rows 0-3 of the group are
-            // w1 rows 4grp..4grp+3, rows 4-7 the w3 rows (llama.cpp:1085-1096)
-            const float a3 = __shfl_xor(res, 32);
-            if (r < 4 && j == 0) {
-                const float sl = f16_to_f32(P.silu_tab[f32_to_f16(res)]);   // ggml_vec_silu_f32 (ggml.c:2495)
-                P.u[grp * 4 + r] = sl * a3;                                  // ggml_mul (llama.cpp:1096)
-            }
-        }
     };
 
     make_table(0, S[0], 0);                 // chunk 0 of the first group
     __builtin_amdgcn_wave_barrier();
+    // a row group: its epilogue's memory operand goes out before its chunk loop (mv_pre_epi)
     if constexpr (XG) {
         for (int k = 0; k + 1 < ng; ++k) {
-            const EpiPre pe = pre_epi(gc);
+            const EpiPre pe = mv_pre_epi<EPI>(P, gc * 8 + r, pos0);
             const float res = body(std::true_type{}, gc, gc + NW);
-            epilogue(gc, res, pe);
+            mv_epilogue<EPI>(P, gc, r, j, res, pos0, pe);
             gc += NW;
         }
     }
-    const EpiPre pe = pre_epi(gc);
+    const EpiPre pe = mv_pre_epi<EPI>(P, gc * 8 + r, pos0);
     const float res = body(std::false_type{}, gc, gc);
-    epilogue(gc, res, pe);
+    mv_epilogue<EPI>(P, gc, r, j, res, pos0, pe);
     LVK_T(3);
 #undef LVK_ISSUE
 }
@@ -524,8 +365,8 @@ __global__ __launch_bounds__((NW + NP) * 64) void k_mv_cu(CuParams P) {
 // -- host -------------------------------------------------------------------
 
 // prologue order (k_mv_cu PF): PFD per launch shape (measured, tools/probe sweeps); the sweep
-// probe build (LVK_PROBE_SWEEP) reads LVK_MV_PF=0..5 to override it for A/B runs, the product
-// library carries only the shipped order
+// probe build (LVK_PROBE_SWEEP) reads LVK_MV_PF (a PfOrder value) to override it for A/B runs, the
+// product library carries only the shipped order
 #ifdef LVK_PROBE_SWEEP
 static int mv_pf_env() {
     static const int v = [] { const char * e = getenv("LVK_MV_PF"); return e ? atoi(e) : -1; }();
@@ -533,7 +374,7 @@ static int mv_pf_env() {
 }
 #endif
 
-template <int NW, int NP, int D, int PRO, int EPI, int KT, int PFD = 2>
+template <int NW, int NP, int D, int PRO, int EPI, int KT, int PFD = PF_TABLE_FIRST>
 hipError_t go(const CuParams & P, hipStream_t s) {
     constexpr int nb = KT / 32, NC = (nb + 31) / 32;
     constexpr bool XG = (NC % D) == 0;
@@ -544,12 +385,11 @@ hipError_t go(const CuParams & P, hipStream_t s) {
 #ifdef LVK_PROBE_SWEEP
     const int pf = mv_pf_env() >= 0 ? mv_pf_env() : PFD;
     switch (pf) {
-        case 0: LVK_LAUNCH((k_mv_cu<NW, NP, D, PRO, EPI, KT, 0>), dim3(nwg), dim3((NW + NP) * 64), lds, s, P); break;
-        case 1: LVK_LAUNCH((k_mv_cu<NW, NP, D, PRO, EPI, KT, 1>), dim3(nwg), dim3((NW + NP) * 64), lds, s, P); break;
-        case 2: LVK_LAUNCH((k_mv_cu<NW, NP, D, PRO, EPI, KT, 2>), dim3(nwg), dim3((NW + NP) * 64), lds, s, P); break;
-        case 3: LVK_LAUNCH((k_mv_cu<NW, NP, D, PRO, EPI, KT, 3>), dim3(nwg), dim3((NW + NP) * 64), lds, s, P); break;
-        case 4: LVK_LAUNCH((k_mv_cu<NW, NP, D, PRO, EPI, KT, 4>), dim3(nwg), dim3((NW + NP) * 64), lds, s, P); break;
-        default: LVK_LAUNCH((k_mv_cu<NW, NP, D, PRO, EPI, KT, 5>), dim3(nwg), dim3((NW + NP) * 64), lds, s, P); break;
+        case PF_ISSUE_FIRST: LVK_LAUNCH((k_mv_cu<NW, NP, D, PRO, EPI, KT, PF_ISSUE_FIRST>), dim3(nwg), dim3((NW + NP) * 64), lds, s, P); break;
+        case PF_INPUTS_LAND: LVK_LAUNCH((k_mv_cu<NW, NP, D, PRO, EPI, KT, PF_INPUTS_LAND>), dim3(nwg), dim3((NW + NP) * 64), lds, s, P); break;
+        case PF_TABLE_FIRST: LVK_LAUNCH((k_mv_cu<NW, NP, D, PRO, EPI, KT, PF_TABLE_FIRST>), dim3(nwg), dim3((NW + NP) * 64), lds, s, P); break;
+        case PF_SPLIT: LVK_LAUNCH((k_mv_cu<NW, NP, D, PRO, EPI, KT, PF_SPLIT>), dim3(nwg), dim3((NW + NP) * 64), lds, s, P); break;
+        default: return hipErrorInvalidValue;
     }
 #else
     LVK_LAUNCH((k_mv_cu<NW, NP, D, PRO, EPI, KT, PFD>), dim3(nwg), dim3((NW + NP) * 64), lds, s, P);
@@ -585,31 +425,16 @@ bool matvec_cu_supported(int K, int qtype) {
     return K == 4096 || K == 11008 || K == 8192 || K == 22016;
 }
 
-namespace {
-CuParams cu_params(const MvLaunch & L) {
-    CuParams P{};
-    P.nib = L.w.nib;
-    P.scl = (const float4 *) L.w.scl;
-    P.G = L.w.M / 8;
-    P.x = L.x + (size_t) L.tok0 * L.w.K;
-    P.g = L.g;
-    P.xq = L.xq;
-    if (P.xq.qs) { P.xq.qs += (size_t) L.tok0 * L.xq.nb; P.xq.d += (size_t) L.tok0 * L.xq.nb; }
-    P.sp = L.sp;
-    P.y = L.y ? L.y + (size_t) L.out_tok0 * L.w.M : nullptr;
-    P.u = L.u;
-    P.q16 = L.q16; P.kc = L.kc; P.vc = L.vc; P.rope = L.rope.cs;
-    P.n_embd = L.n_embd; P.head_dim = L.head_dim; P.n_ctx = L.n_ctx; P.kv32 = L.kv32;
-    P.silu_tab = L.silu_tab;
-    return P;
-}
-}  // namespace
-
 hipError_t launch_matvec_cu(const MvLaunch & L, int pro, int epi, hipStream_t s) {
     if (L.w.qtype == Q4_1) return launch_matvec_cu41(L, pro, epi, s);
     if (L.w.qtype == F16) return launch_matvec_f16(L, pro, epi, s);
     if (L.w.qtype != Q4_0 || L.n_tokens != 1 || L.w.M % 8) return hipErrorNotSupported;
-    const CuParams P = cu_params(L);
+    if (!mv_inputs_set(L, pro)) return hipErrorInvalidValue;
+    CuParams P{};
+    mv_fill(P, L, true);
+    P.nib = L.w.nib;
+    P.scl = (const float4 *) L.w.scl;
+    P.G = L.w.M / 8;
     const int K = L.w.K;
 #ifdef LVK_PROBE_SWEEP   // dev probe builds only: LVK_CFG selects a launch shape
     {
@@ -631,13 +456,13 @@ hipError_t launch_matvec_cu(const MvLaunch & L, int pro, int epi, hipStream_t s)
     // every CU keeps ~60-120 KB of weights in flight
     if (K == 4096) {
         switch (epi) {
-            // prologue order 5 (inputs, chunk 0, table, the rest after the barrier): QKV 7.6 vs
+            // PF_SPLIT (inputs, chunk 0, table, the rest after the barrier): QKV 7.6 vs
             // 7.7-8.4 us, Wo 4.4 vs 4.5-4.9 over orders 0-2 (profiles/r03_pf_sweep.txt)
-            case EPI_QKV: if (pro == PRO_NORM) return go<8, 0, 2, PRO_NORM, EPI_QKV, 4096, 5>(P, s); break;
-            case EPI_SWIGLU_F32: if (pro == PRO_NORM) return go<12, 0, 2, PRO_NORM, EPI_SWIGLU_F32, 4096, 5>(P, s); break;
-            case EPI_STORE: if (pro == PRO_NORM) return go<16, 0, 2, PRO_NORM, EPI_STORE, 4096, 1>(P, s); break;
+            case EPI_QKV: if (pro == PRO_NORM) return go<8, 0, 2, PRO_NORM, EPI_QKV, 4096, PF_SPLIT>(P, s); break;
+            case EPI_SWIGLU_F32: if (pro == PRO_NORM) return go<12, 0, 2, PRO_NORM, EPI_SWIGLU_F32, 4096, PF_SPLIT>(P, s); break;
+            case EPI_STORE: if (pro == PRO_NORM) return go<16, 0, 2, PRO_NORM, EPI_STORE, 4096, PF_INPUTS_LAND>(P, s); break;
             case EPI_RESID:
-                if (pro == PRO_ACTQ) return go<2, 0, 2, PRO_ACTQ, EPI_RESID, 4096, 5>(P, s);
+                if (pro == PRO_ACTQ) return go<2, 0, 2, PRO_ACTQ, EPI_RESID, 4096, PF_SPLIT>(P, s);
                 break;
         }
         // operator API (lvk_mul_mat_q: plain quantize of an f32 input)
@@ -646,10 +471,10 @@ hipError_t launch_matvec_cu(const MvLaunch & L, int pro, int epi, hipStream_t s)
         switch (epi) {
             // prologue orders on the 65B shapes (round-3 sweep, profiles/r03_pf65.txt): 0 for
             // QKV / W1|W3 (22.4 / 38.6 vs 23.1 / 40.1 us at order 2), 5 for Wo (8.2 vs 8.4)
-            case EPI_QKV: if (pro == PRO_NORM) return go<12, 0, 2, PRO_NORM, EPI_QKV, 8192, 0>(P, s); break;
-            case EPI_SWIGLU_F32: if (pro == PRO_NORM) return go<12, 0, 2, PRO_NORM, EPI_SWIGLU_F32, 8192, 0>(P, s); break;
+            case EPI_QKV: if (pro == PRO_NORM) return go<12, 0, 2, PRO_NORM, EPI_QKV, 8192, PF_ISSUE_FIRST>(P, s); break;
+            case EPI_SWIGLU_F32: if (pro == PRO_NORM) return go<12, 0, 2, PRO_NORM, EPI_SWIGLU_F32, 8192, PF_ISSUE_FIRST>(P, s); break;
             case EPI_STORE: if (pro == PRO_NORM) return go<12, 0, 2, PRO_NORM, EPI_STORE, 8192>(P, s); break;
-            case EPI_RESID: if (pro == PRO_ACTQ) return go<4, 0, 2, PRO_ACTQ, EPI_RESID, 8192, 5>(P, s); break;
+            case EPI_RESID: if (pro == PRO_ACTQ) return go<4, 0, 2, PRO_ACTQ, EPI_RESID, 8192, PF_SPLIT>(P, s); break;
         }
         if (epi == EPI_STORE && pro == PRO_ACTF) return go<8, 0, 2, PRO_ACTF, EPI_STORE, 8192>(P, s);
     } else if (K == 11008) {
@@ -660,15 +485,15 @@ hipError_t launch_matvec_cu(const MvLaunch & L, int pro, int epi, hipStream_t s)
         if (epi == EPI_RESID && pro == PRO_ACTF) {
             // (needs at most 2 row groups per CU: a device with fewer CUs takes 8 waves that
             // all quantize u, then issue the weights)
-            const hipError_t e = go<2, 6, 4, PRO_ACTF, EPI_RESID, 11008, 0>(P, s);
+            const hipError_t e = go<2, 6, 4, PRO_ACTF, EPI_RESID, 11008, PF_ISSUE_FIRST>(P, s);
             if (e != hipErrorNotSupported) return e;
-            return go<8, 0, 4, PRO_ACTF, EPI_RESID, 11008, 2>(P, s);
+            return go<8, 0, 4, PRO_ACTF, EPI_RESID, 11008, PF_TABLE_FIRST>(P, s);
         }
         if (epi == EPI_STORE && pro == PRO_ACTF) return go<4, 0, 4, PRO_ACTF, EPI_STORE, 11008>(P, s);
         if (epi == EPI_STORE && pro == PRO_NORM) return go<4, 0, 4, PRO_NORM, EPI_STORE, 11008>(P, s);
     } else if (K == 22016) {
         // 4 compute + 8 prologue waves (the 11008 rule): 20.0 vs 22.1 us (profiles/r03_sweep65.txt)
-        if (epi == EPI_RESID && pro == PRO_ACTF) return go<4, 8, 2, PRO_ACTF, EPI_RESID, 22016, 0>(P, s);
+        if (epi == EPI_RESID && pro == PRO_ACTF) return go<4, 8, 2, PRO_ACTF, EPI_RESID, 22016, PF_ISSUE_FIRST>(P, s);
         if (epi == EPI_STORE && pro == PRO_ACTF) return go<4, 0, 2, PRO_ACTF, EPI_STORE, 22016>(P, s);
         if (epi == EPI_STORE && pro == PRO_NORM) return go<4, 0, 2, PRO_NORM, EPI_STORE, 22016>(P, s);
     }

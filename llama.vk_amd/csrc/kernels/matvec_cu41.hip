@@ -26,25 +26,14 @@ namespace lvk {
 namespace {
 using namespace mv;
 
-struct Cu41Params {
+// (the images lead the block, as in matvec_cu.hip)
+struct Cu41Images {
     const uint4 * nib;
     const float4 * scl;         // [G][NC][2][64]: d, then m
     const uint4 * wsum;         // [G][NC][64]: even-chain weight sums (lvk_kernels.h q41_wsum)
     int G;                      // row groups (M / 8)
-    const float * x;            // PRO_NORM / PRO_ACTF: f32 input [K]
-    const float * g;            // PRO_NORM: norm weight [K]
-    ActQ xq;                    // PRO_ACTQ: quantized input (d, m, qs)
-    const StepParams * sp;
-    float * y;                  // EPI_STORE / EPI_RESID
-    float * u;                  // EPI_SWIGLU_F32: silu(w1 x) * (w3 x) [M/2]
-    uint16_t * q16;
-    uint16_t * kc;
-    uint16_t * vc;
-    const float2 * rope;
-    int n_embd, head_dim, n_ctx;
-    int kv32;                   // f32 KV cache and queries (f16_kv = false)
-    const uint16_t * silu_tab;
 };
+struct Cu41Params : Cu41Images, MvArgs {};
 
 // per-wave block-product tables in LDS: 4 tables (s, dx*my, mx*dy, mx*my) of 8 rows x 32
 // blocks; the row stride is padded to 40 floats so the 8 rows start on banks 0, 40, 16, 56,
@@ -54,15 +43,9 @@ constexpr int SRS = 40, SPL = 8 * SRS, SWF = 4 * SPL;
 
 // SPLIT: only chunk 0 goes out before the activation table, chunks 1..D-1 after the workgroup
 // barrier (the barriers wait for the slowest wave's issue, which the memory system throttles
-// to the return rate once the CU's queue is full; matvec_cu.hip prologue order 5)
-// HALF: the unit of work is a 4-row half group, not an 8-row group: each CU owns an equal share
-// of the 2 G halves and a wave runs two at once (lanes 0-31 and 32-63 read the two 512-byte
-// halves of different groups' 1 KiB slices).  With M = 5120 (13B Wo, W2) every CU then streams
-// exactly 20 rows instead of 16 or 24 (640 groups on 256 CUs).  Not for the W1|W3 epilogue,
-// which pairs the w1 half of a group with its w3 half inside the wave.
-template <int NW, int D, int PRO, int EPI, int KT, int SPLIT = 0, int HALF = 0>
+// to the return rate once the CU's queue is full; matvec_cu.hip PF_SPLIT)
+template <int NW, int D, int PRO, int EPI, int KT, int SPLIT = 0>
 __global__ __launch_bounds__(NW * 64) void k_mv_cu41(Cu41Params P) {
-    static_assert(!(HALF && EPI == EPI_SWIGLU_F32), "W1|W3 pairs the halves of one group");
     constexpr int nb = KT / 32;                 // blocks per row
     constexpr int nsub = nb / 8;                // 8-block sub-chunks (one uint4 per lane each)
     constexpr int NC = (nb + 31) / 32;          // chunks of 32 blocks
@@ -86,29 +69,13 @@ __global__ __launch_bounds__(NW * 64) void k_mv_cu41(Cu41Params P) {
     const int j = lane & 7;
     const int r = lane >> 3;
     const int nwg = gridDim.x;
-    // this CU's work items: row groups [i0, i1) (HALF = 0) or half groups [i0, i1) run in pairs
-    const unsigned NI = HALF ? 2u * (unsigned) P.G : (unsigned) P.G;
-    const int i0 = (int) (blockIdx.x * NI / (unsigned) nwg);
-    const int i1 = (int) ((blockIdx.x + 1) * NI / (unsigned) nwg);
-    const int nitems = HALF ? (i1 - i0 + 1) / 2 : i1 - i0;
-    const int ng = max(0, (nitems - wave + NW - 1) / NW);      // work items of this wave
-    // the lane's half group of item k of this CU: unit (g << 1 | hh), g its group, hh the half;
-    // byte offsets of its slices inside a chunk of each image: lp + hh 512 (lanes 32-63 of a
-    // whole group read the second half); a wave without items reads one word (every lane)
-    auto unit_of = [&](int k, bool & valid) __attribute__((always_inline)) {
-        if constexpr (HALF) {
-            const int raw = i0 + 2 * k + (lane >> 5);
-            valid = raw < i1;
-            return min(raw, i1 - 1);
-        } else {
-            valid = true;
-            return 2 * min(i0 + k, P.G - 1) + (lane >> 5);
-        }
-    };
-    const uint32_t lp = (uint32_t) (lane & 31) * 16u;
-    int gc = wave;           // item index of the wave's current row group / half-group pair
+    // this CU's row groups [g0, g1)
+    const int g0 = (int) (blockIdx.x * (unsigned) P.G / (unsigned) nwg);
+    const int g1 = (int) ((blockIdx.x + 1) * (unsigned) P.G / (unsigned) nwg);
+    const int ng = max(0, (g1 - g0 - wave + NW - 1) / NW);      // row groups of this wave
+    int gc = min(g0 + wave, P.G - 1);
     // the QKV epilogue's position, loaded ahead of the inputs so that the RoPE pair can be loaded at
-    // an item's start (pre_epi; matvec_cu.hip has the measurements)
+    // a row group's start (mv_pre_epi)
     [[maybe_unused]] int pos0 = 0;
     if constexpr (EPI == EPI_QKV)
         pos0 = __hip_atomic_load((const __attribute__((address_space(1))) int *) &P.sp->n_past, __ATOMIC_RELAXED,
@@ -122,16 +89,7 @@ __global__ __launch_bounds__(NW * 64) void k_mv_cu41(Cu41Params P) {
     uint4 qv[FPRO ? 1 : UM];
     float dv[FPRO ? 1 : UM], mv_[FPRO ? 1 : UM];
     if constexpr (FPRO) {
-#pragma unroll
-        for (int k = 0; k < UM; ++k) {
-            const int un = min(k * NT + tid, nunits - 1);
-            const float4 * xp = (const float4 *) (P.x + (size_t) un * 8);
-            xv[k][0] = xp[0]; xv[k][1] = xp[1];
-            if constexpr (PRO == PRO_NORM) {
-                const float4 * gp = (const float4 *) (P.g + (size_t) un * 8);
-                gv[k][0] = gp[0]; gv[k][1] = gp[1];
-            }
-        }
+        pro_load_units<NT, PRO>(P.x, P.g, nunits, tid, xv, gv);
     } else {
 #pragma unroll
         for (int k = 0; k < UM; ++k) {
@@ -142,18 +100,17 @@ __global__ __launch_bounds__(NW * 64) void k_mv_cu41(Cu41Params P) {
         }
     }
 
-    // first D chunks of this wave's first item.  Per chunk c of group g the images hold
+    // first D chunks of this wave's first row group.  Per chunk c of group g the images hold
     // nib [g][c][4 sub][1 KiB], d | m [g][c][2][1 KiB], wsum [g][c][1 KiB]; a lane's slice of
-    // each 1 KiB is 16 bytes at (hh 512 + lp).  Lane bases per item: lb_n / lb_s / lb_w.
+    // each 1 KiB is its 16 bytes; a wave without row groups reads one word (every lane).  Lane
+    // bases per group: lb_n / lb_s / lb_w.
     uint4 W[D][4];
     uint4 WS[D];
     float4 SD[D], SM[D];
-    size_t lb_n, lb_s, lb_w;          // the current item's lane bases
-    auto lane_bases = [&](int k, size_t & bn, size_t & bs, size_t & bw) __attribute__((always_inline)) {
-        bool v;
-        const int u = unit_of(k, v);
-        const size_t gq = (size_t) (u >> 1) * NC;
-        const uint32_t o = ng > 0 ? (uint32_t) (u & 1) * 512u + lp : 0u;
+    size_t lb_n, lb_s, lb_w;          // the current group's lane bases
+    auto lane_bases = [&](int grp, size_t & bn, size_t & bs, size_t & bw) __attribute__((always_inline)) {
+        const size_t gq = (size_t) grp * NC;
+        const uint32_t o = ng > 0 ? (uint32_t) lane * 16u : 0u;
         bn = gq * 4096 + o;
         bs = gq * 2048 + o;
         bw = gq * 1024 + o;
@@ -176,18 +133,8 @@ __global__ __launch_bounds__(NW * 64) void k_mv_cu41(Cu41Params P) {
     if constexpr (FPRO) {
         float scale = 1.0f;
         if constexpr (PRO == PRO_NORM) {
-            // ggml_compute_forward_rms_norm_f32 (ggml.c:6058-6076): float squares summed
-            // in double; per-thread units, a DPP wave tree, the NW wave sums in order
-            double acc = 0.0;
-#pragma unroll
-            for (int k = 0; k < UM; ++k) {
-                if (k * NT + tid < nunits) {
-                    const float e[8] = {xv[k][0].x, xv[k][0].y, xv[k][0].z, xv[k][0].w,
-                                        xv[k][1].x, xv[k][1].y, xv[k][1].z, xv[k][1].w};
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) { const float sq = e[q] * e[q]; acc += (double) sq; }
-                }
-            }
+            // per-thread units, a DPP wave tree, the NW wave sums in order (RMSNorm order)
+            double acc = pro_sumsq_units<NT>(xv, nunits, tid);
             acc = wave_sum_d(acc);
             if (lane == 0) red[wave] = acc;
             __syncthreads();
@@ -196,40 +143,12 @@ __global__ __launch_bounds__(NW * 64) void k_mv_cu41(Cu41Params P) {
             const float mean = rms_mean_wave(sum, P.x, KT);
             scale = 1.0f / sqrtf(mean + 1e-6f);
         }
-#pragma unroll
-        for (int k = 0; k < UM; ++k) {
-            if (k * NT >= nunits) break;
-            const int un = k * NT + tid;
-            float v[8] = {xv[k][0].x, xv[k][0].y, xv[k][0].z, xv[k][0].w,
-                          xv[k][1].x, xv[k][1].y, xv[k][1].z, xv[k][1].w};
-            if constexpr (PRO == PRO_NORM) {
-                const float gg[8] = {gv[k][0].x, gv[k][0].y, gv[k][0].z, gv[k][0].w,
-                                     gv[k][1].x, gv[k][1].y, gv[k][1].z, gv[k][1].w};
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float yn = v[e] * scale;      // ggml_vec_scale_f32 (ggml.c:6076)
-                    v[e] = gg[e] * yn;                  // ggml_mul(repeat(g), cur) (llama.cpp:984)
-                }
-            }
-            // the 4 units of a block are a lane quad (nunits % 4 == 0, NT % 4 == 0)
-            float d, m;
-            uint32_t qw;
-            q41_quad(v, d, m, qw);
-            uint32_t qs[4];
-            qs[0] = __builtin_bit_cast(uint32_t, quad_bcast<0>(__builtin_bit_cast(float, qw)));
-            qs[1] = __builtin_bit_cast(uint32_t, quad_bcast<1>(__builtin_bit_cast(float, qw)));
-            qs[2] = __builtin_bit_cast(uint32_t, quad_bcast<2>(__builtin_bit_cast(float, qw)));
-            qs[3] = __builtin_bit_cast(uint32_t, quad_bcast<3>(__builtin_bit_cast(float, qw)));
-            if (un < nunits && (un & 3) == 0) act41_store(act, dyv, myv, ys, un >> 2, qs, d, m);
-        }
+        pro_q41_units<NT, PRO>(xv, gv, scale, nunits, tid, act, dyv, myv, ys);
     } else {
 #pragma unroll
         for (int k = 0; k < UM; ++k) {
             const int b = k * NT + tid;
-            if (b < nb) {
-                const uint32_t qs[4] = {qv[k].x, qv[k].y, qv[k].z, qv[k].w};
-                act41_store(act, dyv, myv, ys, b, qs, dv[k], mv_[k]);
-            }
+            if (b < nb) q41_block_store(act, dyv, myv, ys, b, qv[k], dv[k], mv_[k]);
         }
     }
     __syncthreads();            // activation table ready
@@ -246,7 +165,7 @@ __global__ __launch_bounds__(NW * 64) void k_mv_cu41(Cu41Params P) {
     auto body = [&](auto has_next, float & off) __attribute__((always_inline)) {
         float acc = 0.0f;
         off = 0.0f;
-        size_t nb_n = 0, nb_s = 0, nb_w = 0;        // the next item's lane bases (cross-item prefetch)
+        size_t nb_n = 0, nb_s = 0, nb_w = 0;        // the next group's lane bases (cross-group prefetch)
         if constexpr (decltype(has_next)::value) lane_bases(gc + NW, nb_n, nb_s, nb_w);
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
@@ -328,77 +247,34 @@ __global__ __launch_bounds__(NW * 64) void k_mv_cu41(Cu41Params P) {
         return octet_reduce(acc);
     };
 
-    // the epilogue's memory operand of an item (the lane's RoPE pair, or the residual term), loaded
-    // before the item's chunk loop instead of in the wave's tail (as matvec_cu.hip)
-    struct EpiPre { float2 cs; float rv; };
-    auto pre_epi = [&](int item) __attribute__((always_inline)) {
-        EpiPre e{make_float2(0.0f, 0.0f), 0.0f};
-        if constexpr (EPI == EPI_QKV || EPI == EPI_RESID) {
-            bool valid;
-            const int u = unit_of(item, valid);
-            const int row = (u >> 1) * 8 + (u & 1) * 4 + (r & 3);
-            if constexpr (EPI == EPI_QKV) {
-                const int i0 = (row - (row / P.n_embd) * P.n_embd) % P.head_dim;   // V rows: an unused pair
-                e.cs = P.rope[(size_t) pos0 * (P.head_dim / 2) + (i0 >> 1)];
-            } else {
-                e.rv = P.y[row];
-            }
-        }
-        return e;
-    };
-    auto epilogue = [&](int item, float h, float off, const EpiPre & pe) __attribute__((always_inline)) {
-        const float res = h + off * 32.0f;        // acc_offset * QK (ggml.c:2249)
-        bool valid;
-        const int u = unit_of(item, valid);
-        const int grp = u >> 1;
-        const int row = grp * 8 + (u & 1) * 4 + (r & 3);
-        if constexpr (EPI == EPI_STORE) {
-            if (j == 0 && valid) P.y[row] = res;
-        } else if constexpr (EPI == EPI_RESID) {
-            if (j == 0 && valid) P.y[row] = res + pe.rv;         // ggml_add(cur, inpSA) (llama.cpp:1071,1103)
-        } else if constexpr (EPI == EPI_QKV) {
-            // (a duplicated half, !valid, recomputed its original's rows bit for bit: its stores
-            // write the same values, and the RoPE partner exchange stays convergent)
-            qkv_epilogue_cs(res, row, j, P.n_embd, P.head_dim, pos0, pe.cs, P.q16, P.kc, P.vc, P.n_ctx, P.kv32);
-        } else if constexpr (EPI == EPI_SWIGLU_F32) {
-            // fused W1|W3 image interleaved per 4 rows: rows 0-3 of the group are
-            // w1 rows 4grp..4grp+3, rows 4-7 the w3 rows (llama.cpp:1085-1096)
-            const float a3 = __shfl_xor(res, 32);
-            if (r < 4 && j == 0) {
-                const float sl = f16_to_f32(P.silu_tab[f32_to_f16(res)]);   // ggml_vec_silu_f32 (ggml.c:2495)
-                P.u[grp * 4 + r] = sl * a3;                                  // ggml_mul (llama.cpp:1096)
-            }
-        }
-    };
-
+    // a row group: its epilogue's memory operand goes out before its chunk loop (mv_pre_epi);
+    // res = hsum(acc) + acc_offset * QK (ggml.c:2249)
     if constexpr (XG) {
         for (int k = 0; k + 1 < ng; ++k) {
             float off;
-            const EpiPre pe = pre_epi(gc);
+            const EpiPre pe = mv_pre_epi<EPI>(P, gc * 8 + r, pos0);
             const float h = body(std::true_type{}, off);
-            epilogue(gc, h, off, pe);
+            mv_epilogue<EPI>(P, gc, r, j, h + off * 32.0f, pos0, pe);
             gc += NW;
             lane_bases(gc, lb_n, lb_s, lb_w);
         }
     }
     float off;
-    const EpiPre pe = pre_epi(gc);
+    const EpiPre pe = mv_pre_epi<EPI>(P, gc * 8 + r, pos0);
     const float h = body(std::false_type{}, off);
-    epilogue(gc, h, off, pe);
+    mv_epilogue<EPI>(P, gc, r, j, h + off * 32.0f, pos0, pe);
 #undef LVK_ISSUE41
 }
 
-template <int NW, int D, int PRO, int EPI, int KT, int SPLIT = 0, int HALF = 0>
+template <int NW, int D, int PRO, int EPI, int KT, int SPLIT = 0>
 hipError_t go(const Cu41Params & P, hipStream_t s) {
     constexpr int nb = KT / 32, NC = (nb + 31) / 32;
     constexpr bool XG = (NC % D) == 0;
     const int nwg = std::min(cu_count(), P.G);
-    // work items per CU (row groups, or pairs of half groups): without cross-group prefetch
-    // every wave must own at most one
-    const int items = HALF ? ((2 * P.G + nwg - 1) / nwg + 1) / 2 : (P.G + nwg - 1) / nwg;
-    if (!XG && items > NW) return hipErrorNotSupported;
+    // without cross-group prefetch every wave must own at most one row group
+    if (!XG && (P.G + nwg - 1) / nwg > NW) return hipErrorNotSupported;
     const size_t lds = (size_t) nb * 32 + 2 * NC * 128 + (size_t) nb * 16 + NW * SWF * 4 + NW * 8;
-    LVK_LAUNCH((k_mv_cu41<NW, D, PRO, EPI, KT, SPLIT, HALF>), dim3(nwg), dim3(NW * 64), lds, s, P);
+    LVK_LAUNCH((k_mv_cu41<NW, D, PRO, EPI, KT, SPLIT>), dim3(nwg), dim3(NW * 64), lds, s, P);
     return hipGetLastError();
 }
 
@@ -408,33 +284,14 @@ bool matvec_cu41_supported(int K) { return K == 4096 || K == 5120 || K == 11008 
 
 hipError_t launch_matvec_cu41(const MvLaunch & L, int pro, int epi, hipStream_t s) {
     if (L.w.qtype != Q4_1 || L.n_tokens != 1 || L.w.M % 8) return hipErrorNotSupported;
+    if (!mv_inputs_set(L, pro)) return hipErrorInvalidValue;
     Cu41Params P{};
+    mv_fill(P, L, true);
     P.nib = L.w.nib;
     P.scl = (const float4 *) L.w.scl;
     P.wsum = q41_wsum(L.w);
     P.G = L.w.M / 8;
-    P.x = L.x ? L.x + (size_t) L.tok0 * L.w.K : nullptr;
-    P.g = L.g;
-    P.xq = L.xq;
-    if (P.xq.qs) {
-        P.xq.qs += (size_t) L.tok0 * L.xq.nb;
-        P.xq.d += (size_t) L.tok0 * L.xq.nb;
-        P.xq.m += (size_t) L.tok0 * L.xq.nb;
-    }
-    P.sp = L.sp;
-    P.y = L.y ? L.y + (size_t) L.out_tok0 * L.w.M : nullptr;
-    P.u = L.u;
-    P.q16 = L.q16; P.kc = L.kc; P.vc = L.vc; P.rope = L.rope.cs;
-    P.n_embd = L.n_embd; P.head_dim = L.head_dim; P.n_ctx = L.n_ctx; P.kv32 = L.kv32;
-    P.silu_tab = L.silu_tab;
     const int K = L.w.K;
-    // half-group work units (HALF) where they even out the rows per CU: opt-in (LVK_MV41_HALF=1).
-    // Measured on 13B (profiles/r05_ab13.jsonl): 312.1 / 312.4 tok/s against 319.3 / 312.0 with
-    // whole groups, Wo 7.4 vs 6.9-7.3 us, W2 19.3 vs 18.9-19.5 us -- the 20 % byte imbalance of
-    // M = 5120 is not what sets these kernels' time (each wave's serial chain is)
-    static const bool half_env = [] { const char * e = getenv("LVK_MV41_HALF"); return e && atoi(e) != 0; }();
-    const int nwg = std::min(cu_count(), P.G);
-    const bool half = half_env && P.G % nwg != 0 && (2 * P.G) % nwg == 0;
 #ifdef LVK_PROBE_SWEEP   // dev probe builds only: LVK_CFG41 selects a launch shape (waves, prefetch depth)
     {
         static int cfg = getenv("LVK_CFG41") ? atoi(getenv("LVK_CFG41")) : 0;
@@ -478,10 +335,7 @@ hipError_t launch_matvec_cu41(const MvLaunch & L, int pro, int epi, hipStream_t 
             // SPLIT (chunk 1 after the table barrier): 16.9 vs 17.5 us, W2 19.5 vs 19.8
             // (profiles/r03_sweep13_split.txt)
             case EPI_QKV:
-                if (pro == PRO_NORM) {
-                    if (half) return go<8, 2, PRO_NORM, EPI_QKV, 5120, 1, 1>(P, s);
-                    return go<8, 2, PRO_NORM, EPI_QKV, 5120, 1>(P, s);
-                }
+                if (pro == PRO_NORM) return go<8, 2, PRO_NORM, EPI_QKV, 5120, 1>(P, s);
                 break;
             case EPI_SWIGLU_F32: if (pro == PRO_NORM) return go<8, 1, PRO_NORM, EPI_SWIGLU_F32, 5120>(P, s); break;
             case EPI_STORE:
@@ -489,19 +343,13 @@ hipError_t launch_matvec_cu41(const MvLaunch & L, int pro, int epi, hipStream_t 
                 if (pro == PRO_ACTF) return go<8, 1, PRO_ACTF, EPI_STORE, 5120>(P, s);
                 break;
             case EPI_RESID:
-                if (pro == PRO_ACTQ) {
-                    if (half) return go<3, 2, PRO_ACTQ, EPI_RESID, 5120, 0, 1>(P, s);
-                    return go<3, 2, PRO_ACTQ, EPI_RESID, 5120>(P, s);
-                }
+                if (pro == PRO_ACTQ) return go<3, 2, PRO_ACTQ, EPI_RESID, 5120>(P, s);
                 break;
         }
     } else if (K == 13824) {
         // 8 waves: the 5-6 without a row group help quantize u (r03 sweep: 19.9 vs 20.9 us;
         // D = 7 / 14 with 4 waves: 23.5 / 28.3)
-        if (epi == EPI_RESID && pro == PRO_ACTF) {
-            if (half) return go<8, 2, PRO_ACTF, EPI_RESID, 13824, 1, 1>(P, s);
-            return go<8, 2, PRO_ACTF, EPI_RESID, 13824, 1>(P, s);
-        }
+        if (epi == EPI_RESID && pro == PRO_ACTF) return go<8, 2, PRO_ACTF, EPI_RESID, 13824, 1>(P, s);
         if (epi == EPI_STORE && pro == PRO_ACTF) return go<4, 2, PRO_ACTF, EPI_STORE, 13824>(P, s);
     } else if (K == 4096) {
         switch (epi) {

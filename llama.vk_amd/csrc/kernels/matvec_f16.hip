@@ -15,21 +15,11 @@ namespace lvk {
 namespace {
 using namespace f16k;
 
-struct F16Params {
+struct F16Image {
     const uint4 * img;
     int M, K, G;                // G = row groups, ceil(M / 8)
-    const float * x;            // f32 input row [K]
-    const float * g;            // PRO_NORM: norm weight [K]
-    const StepParams * sp;
-    float * y;                  // EPI_STORE / EPI_RESID row [M]
-    float * u;                  // EPI_SWIGLU_F32 [M / 2]
-    uint16_t * q16;
-    uint16_t * kc;
-    uint16_t * vc;
-    const float2 * rope;
-    int n_embd, head_dim, n_ctx, kv32;
-    const uint16_t * silu_tab;
 };
+struct F16Params : F16Image, mv::MvArgs {};
 
 constexpr int D = 16;           // 16-byte weight loads in flight per lane (16 KiB per wave)
 
@@ -87,23 +77,12 @@ __global__ __launch_bounds__(NW * 64) void k_matvec_f16(F16Params P) {
     }
 
     const float res = chain_reduce(acc);
+    // the epilogue's memory operand (RoPE pair, residual term) is loaded here, in the tail
+    [[maybe_unused]] int pos0 = 0;
+    if constexpr (EPI == EPI_QKV) pos0 = P.sp->n_past;
     const int row = grp * 8 + r;
-    if constexpr (EPI == EPI_STORE) {
-        if (c == 0 && row < P.M) P.y[row] = res;
-    } else if constexpr (EPI == EPI_RESID) {
-        // ggml_add(cur, inpSA) (llama.cpp:1071,1103)
-        if (c == 0 && row < P.M) P.y[row] = res + P.y[row];
-    } else if constexpr (EPI == EPI_QKV) {
-        mv::qkv_epilogue(res, row, c, P.n_embd, P.head_dim, P.sp->n_past, P.rope, P.q16, P.kc, P.vc, P.n_ctx, P.kv32);
-    } else if constexpr (EPI == EPI_SWIGLU_F32) {
-        // fused W1|W3 image interleaved per 4 rows: rows 0-3 of the group are w1 rows
-        // 4grp .. 4grp+3, rows 4-7 the matching w3 rows (llama.cpp:1085-1096)
-        const float a3 = __shfl_xor(res, 32);
-        if (r < 4 && c == 0) {
-            const float sl = f16_to_f32(P.silu_tab[f32_to_f16(res)]);   // ggml_vec_silu_f32 (ggml.c:2495)
-            P.u[grp * 4 + r] = sl * a3;                                  // ggml_mul (llama.cpp:1096)
-        }
-    }
+    const mv::EpiPre pe = mv::mv_pre_epi<EPI>(P, row, pos0);
+    mv::mv_epilogue<EPI>(P, grp, r, c, res, pos0, pe, row < P.M);
 }
 
 // file-layout f16 rows -> paired-step octet image, one thread per 16-byte unit.  Rows past M
@@ -161,17 +140,12 @@ hipError_t launch_matvec_f16(const MvLaunch & L, int pro, int epi, hipStream_t s
     if (L.w.qtype != F16 || L.n_tokens != 1) return hipErrorNotSupported;
     if (L.w.K % 256 || L.w.M < 1) return hipErrorInvalidValue;
     if (epi != EPI_STORE && L.w.M % 8) return hipErrorInvalidValue;
+    if (pro == PRO_ACTQ) return hipErrorNotSupported;       // f16 weights take f32 rows
+    if (!mv::mv_inputs_set(L, pro)) return hipErrorInvalidValue;
     F16Params P{};
+    mv::mv_fill(P, L, true);
     P.img = L.w.nib;
     P.M = L.w.M; P.K = L.w.K; P.G = (L.w.M + 7) / 8;
-    P.x = L.x ? L.x + (size_t) L.tok0 * L.w.K : nullptr;
-    P.g = L.g; P.sp = L.sp;
-    P.y = L.y ? L.y + (size_t) L.out_tok0 * L.w.M : nullptr;
-    P.u = L.u;
-    P.q16 = L.q16; P.kc = L.kc; P.vc = L.vc; P.rope = L.rope.cs;
-    P.n_embd = L.n_embd; P.head_dim = L.head_dim; P.n_ctx = L.n_ctx; P.kv32 = L.kv32;
-    P.silu_tab = L.silu_tab;
-    if (!P.x || (pro == PRO_NORM && !P.g)) return hipErrorInvalidValue;
     if (pro == PRO_NORM) {
         switch (epi) {
             case EPI_STORE: return go_nw<PRO_NORM, EPI_STORE>(P, s);

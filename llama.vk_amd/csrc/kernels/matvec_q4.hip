@@ -35,32 +35,22 @@ using namespace mv;
 
 constexpr int CB = 32;    // blocks per chunk (one float4 of scales per lane)
 
-struct Params {
+struct Image {
     const uint4 * nib;
     const float4 * scl;
     int M, K, nb, NC;
-    const float * x;
-    const float * g;
-    ActQ xq;
-    const StepParams * sp;
-    int n_tokens, tok0, out_tok0;
-    float * y;
-    uint16_t * q16;
-    uint16_t * kc;
-    uint16_t * vc;
-    const float2 * rope;
-    int n_embd, head_dim, n_ctx;
-    int kv32;                   // f32 KV cache and queries (f16_kv = false)
-    const uint16_t * silu_tab;
-    ActQ out_q;
+};
+struct Params : Image, MvArgs {
+    int n_tokens, tok0;         // the token window: rows tok0 .. tok0 + n_tokens - 1 of x / xq
+    ActQ out_q;                 // EPI_SWIGLU: quantized u
 };
 
 // ---------------------------------------------------------------------------
 // Prologue A (PRO_NORM): x[t] -> rms_norm -> * g -> quantize_row_q4_0, into
-// the LDS table.  ggml.c:6058-6076 then llama.cpp:984.  The double sum of
+// the LDS table (the pieces of matvec_common.h).  The double sum of
 // squares is reduced as a tree; rms_mean (lvk_device.h) returns the index-order
 // mean (a re-sum when the tree's lies near a float rounding boundary).
-// Work unit = 8 consecutive elements; a block's 4 units are a thread quad.
+// PRE (one token): the units are in registers already (xv, gv).
 // ---------------------------------------------------------------------------
 template <int NT, int T, int UMAX, bool PRE>
 __device__ void prologue_norm(const Params & P, int t0, int nt, uint32_t * act_base, float * dxp_base,
@@ -69,30 +59,27 @@ __device__ void prologue_norm(const Params & P, int t0, int nt, uint32_t * act_b
     const int tid = threadIdx.x;
     const int K = P.K;
     const int nunits = K / 8;
-    auto ldx = [&](int tt, int k, float v[8]) {
-        float4 a, b;
-        if constexpr (PRE) { a = xv[k][0]; b = xv[k][1]; }
-        else {
+    // unit k of token tt: x, and with_g the norm weight (zeros past the row's end)
+    auto ld = [&](int tt, int k, bool with_g, float4 (&x2)[2], float4 (&g2)[2]) {
+        const float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        x2[0] = x2[1] = g2[0] = g2[1] = z;
+        if (k * NT + tid >= nunits) return;
+        if constexpr (PRE) {
+            x2[0] = xv[k][0]; x2[1] = xv[k][1]; g2[0] = gv[k][0]; g2[1] = gv[k][1];
+        } else {
             const float4 * xp = (const float4 *) (P.x + (size_t) (P.tok0 + t0 + tt) * K + (size_t) (k * NT + tid) * 8);
-            a = xp[0]; b = xp[1];
+            x2[0] = xp[0]; x2[1] = xp[1];
+            if (with_g) { const float4 * gp = (const float4 *) (P.g + (size_t) (k * NT + tid) * 8); g2[0] = gp[0]; g2[1] = gp[1]; }
         }
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-    };
-    auto ldg = [&](int k, float v[8]) {
-        float4 a, b;
-        if constexpr (PRE) { a = gv[k][0]; b = gv[k][1]; }
-        else { const float4 * gp = (const float4 *) (P.g + (size_t) (k * NT + tid) * 8); a = gp[0]; b = gp[1]; }
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
     };
     for (int tt = 0; tt < T; ++tt) {
         double acc = 0.0;
 #pragma unroll
         for (int k = 0; k < UMAX; ++k) {
             if (k * NT + tid < nunits && tt < nt) {
-                float e[8];
-                ldx(tt, k, e);
-#pragma unroll
-                for (int q = 0; q < 8; ++q) { const float sq = e[q] * e[q]; acc += (double) sq; }
+                float4 x2[2], g2[2];
+                ld(tt, k, false, x2, g2);
+                sumsq4(acc, x2[0]); sumsq4(acc, x2[1]);
             }
         }
         acc = warp_sum_d(acc);
@@ -115,29 +102,12 @@ __device__ void prologue_norm(const Params & P, int t0, int nt, uint32_t * act_b
         for (int k = 0; k < UMAX; ++k) {
             if (k * NT >= nunits) break;
             const int u = k * NT + tid;
-            const bool live = u < nunits;
-            float v[8], gg[8];
-            if (live) { ldx(tt, k, v); ldg(k, gg); }
-            else {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) { v[e] = 0.0f; gg[e] = 0.0f; }
-            }
-            float amax = 0.0f;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float yn = v[e] * scale;      // ggml_vec_scale_f32 (ggml.c:6076)
-                v[e] = gg[e] * yn;                  // ggml_mul(repeat(g), cur) (llama.cpp:984)
-                const float a = fabsf(v[e]);
-                amax = a > amax ? a : amax;
-            }
-            const float o0 = quad_bcast<0>(amax), o1 = quad_bcast<1>(amax);
-            const float o2 = quad_bcast<2>(amax), o3 = quad_bcast<3>(amax);
-            const float m01 = o1 > o0 ? o1 : o0, m23 = o3 > o2 ? o3 : o2;
-            amax = m23 > m01 ? m23 : m01;
-            const float d = amax / 7.0f;                              // ggml.c:651
-            const float id = (amax != 0.0f) ? 7.0f / amax : 0.0f;     // ggml.c:653
-            const uint32_t w = q40_pack8(v, id);
-            if (live) act_store(act, dxp, u >> 2, u & 3, w, d, (u & 3) == 0);
+            float4 x2[2], g2[2];
+            ld(tt, k, true, x2, g2);
+            float v[8];
+            unit_vals(x2[0], x2[1], v);
+            pro_norm_unit<PRO_NORM>(v, g2[0], g2[1], scale);
+            q40_unit_store(v, u, u < nunits, act, dxp);
         }
     }
 }
@@ -151,26 +121,15 @@ __device__ void prologue_actq(const Params & P, int t0, int nt, uint32_t * act_b
 #pragma unroll
         for (int k = 0; k < BMAX; ++k) {
             const int b = k * NT + tid;
-            if (b < P.nb) {
-                act_store(act_base, dxp_base, b, 0, qv[k].x, dv[k], true);
-                act_store(act_base, dxp_base, b, 1, qv[k].y, 0.0f, false);
-                act_store(act_base, dxp_base, b, 2, qv[k].z, 0.0f, false);
-                act_store(act_base, dxp_base, b, 3, qv[k].w, 0.0f, false);
-            }
+            if (b < P.nb) q40_block_store(act_base, dxp_base, b, qv[k], dv[k]);
         }
     } else {
         for (int tt = 0; tt < nt; ++tt) {
             const int t = t0 + tt + P.tok0;
             uint32_t * act = act_base + (size_t) tt * P.nb * 8;
             float * dxp = dxp_base + (size_t) tt * P.NC * 32;
-            for (int b = tid; b < P.nb; b += NT) {
-                const uint4 qs = P.xq.qs[(size_t) t * P.nb + b];
-                const float d = P.xq.d[(size_t) t * P.nb + b];
-                act_store(act, dxp, b, 0, qs.x, d, true);
-                act_store(act, dxp, b, 1, qs.y, 0.0f, false);
-                act_store(act, dxp, b, 2, qs.z, 0.0f, false);
-                act_store(act, dxp, b, 3, qs.w, 0.0f, false);
-            }
+            for (int b = tid; b < P.nb; b += NT)
+                q40_block_store(act, dxp, b, P.xq.qs[(size_t) t * P.nb + b], P.xq.d[(size_t) t * P.nb + b]);
         }
     }
 }
@@ -214,17 +173,8 @@ __global__ __launch_bounds__(NT) void k_matvec_q40(Params P) {
     float4 gv[UM][2];
     uint4 qv[UM];
     float dv[UM];
-    if constexpr (PRE && PRO == PRO_NORM) {
-        const int nunits = K / 8;
-#pragma unroll
-        for (int k = 0; k < UM; ++k) {
-            const int u = min(k * NT + tid, nunits - 1);
-            const float4 * gp = (const float4 *) (P.g + (size_t) u * 8);
-            const float4 * xp = (const float4 *) (P.x + (size_t) (P.tok0 + t0) * K + (size_t) u * 8);
-            gv[k][0] = gp[0]; gv[k][1] = gp[1];
-            xv[k][0] = xp[0]; xv[k][1] = xp[1];
-        }
-    }
+    if constexpr (PRE && PRO == PRO_NORM)
+        pro_load_units<NT, PRO_NORM>(P.x + (size_t) (P.tok0 + t0) * K, P.g, K / 8, tid, xv, gv);
     if constexpr (PRE && PRO == PRO_ACTQ) {
 #pragma unroll
         for (int k = 0; k < UM; ++k) {
@@ -340,41 +290,8 @@ __global__ __launch_bounds__(NT) void k_matvec_q40(Params P) {
 #pragma unroll
     for (int tt = 0; tt < T; ++tt) res[tt] = octet_reduce(acc[tt]);
 
-    if constexpr (EPI == EPI_STORE) {
-#pragma unroll
-        for (int tt = 0; tt < T; ++tt)
-            if (tt < nt && j == 0) P.y[(size_t) (P.out_tok0 + t0 + tt) * P.M + row] = res[tt];
-    } else if constexpr (EPI == EPI_RESID) {
-#pragma unroll
-        for (int tt = 0; tt < T; ++tt)
-            if (tt < nt && j == 0) {
-                float * yp = P.y + (size_t) (P.out_tok0 + t0 + tt) * P.M + row;
-                *yp = res[tt] + *yp;                 // ggml_add(cur, inpSA) (llama.cpp:1071,1103)
-            }
-    } else if constexpr (EPI == EPI_QKV) {
-        const int E = P.n_embd, hd = P.head_dim;
-        const int which = row / E;          // 0 q, 1 k, 2 v (uniform per wave: E % 8 == 0)
-        const int e = row - which * E;
-        const int n_past = P.sp->n_past;
-#pragma unroll
-        for (int tt = 0; tt < T; ++tt) {
-            const float other = __shfl_xor(res[tt], 8);   // row e^1 lives in lanes of row r^1
-            if (tt < nt && j == 0) {
-                const int pos = n_past + t0 + tt;
-                if (which < 2) {
-                    // ggml_compute_forward_rope_f32 mode 0 (ggml.c:7209-7223)
-                    const int i0 = e % hd;
-                    const float2 cs = P.rope[(size_t) pos * (hd / 2) + (i0 >> 1)];
-                    float out;
-                    if ((i0 & 1) == 0) { const float a = res[tt] * cs.x, b = other * cs.y; out = a - b; }
-                    else               { const float a = other * cs.y, b = res[tt] * cs.x; out = a + b; }
-                    if (which == 0) kv_store(P.q16, (size_t) (t0 + tt) * E + e, out, P.kv32);
-                    else            kv_store(P.kc, (size_t) pos * E + e, out, P.kv32);
-                } else {
-                    kv_store(P.vc, (size_t) e * P.n_ctx + pos, res[tt], P.kv32);
-                }
-            }
-        }
+    if constexpr (EPI != EPI_SWIGLU) {
+        mv_epilogue_rows<T, EPI>(P, res, row, j, P.M, t0, nt);
     } else if constexpr (EPI == EPI_SWIGLU) {
         // WG = 8 waves = rows [64b, 64b+64) of the fused W1|W3 image, which is
         // interleaved per 4 rows: wave k rows 0-3 are w1 rows 32b+4k..+3, rows
@@ -391,9 +308,8 @@ __global__ __launch_bounds__(NT) void k_matvec_q40(Params P) {
             const int e = lane & 31;
             const float a1 = ures[tt * 64 + (e >> 2) * 8 + (e & 3)];        // w1 x
             const float a3 = ures[tt * 64 + (e >> 2) * 8 + 4 + (e & 3)];    // w3 x
-            const float sl = f16_to_f32(P.silu_tab[f32_to_f16(a1)]);   // ggml_vec_silu_f32 (ggml.c:2495)
-            const float u = sl * a3;                                    // ggml_mul (llama.cpp:1096)
-            const int t = P.out_tok0 + t0 + tt;
+            const float u = silu_mul(a1, a3, P.silu_tab);
+            const int t = t0 + tt;
             quantize32_q40(u, lane, P.out_q.d + (size_t) t * P.out_q.nb + blk,
                            P.out_q.qs + (size_t) t * P.out_q.nb + blk, scratch + (tid >> 5) * 4);
         }
@@ -434,24 +350,26 @@ hipError_t launch_matvec(const MvLaunch & L, int pro, int epi, hipStream_t s) {
     if (L.w.qtype != Q4_0) return hipErrorNotSupported;
     if (L.w.M % 8 || L.w.K % 256) return hipErrorInvalidValue;
     Params P{};
+    mv_fill(P, L, false);
     P.nib = L.w.nib;
     P.scl = (const float4 *) L.w.scl;
     P.M = L.w.M; P.K = L.w.K; P.nb = L.w.K / 32; P.NC = (P.nb + CB - 1) / CB;
-    P.x = L.x; P.g = L.g; P.xq = L.xq; P.sp = L.sp;
-    P.n_tokens = L.n_tokens; P.tok0 = L.tok0; P.out_tok0 = L.out_tok0;
-    P.y = L.y; P.q16 = L.q16; P.kc = L.kc; P.vc = L.vc; P.rope = L.rope.cs;
-    P.n_embd = L.n_embd; P.head_dim = L.head_dim; P.n_ctx = L.n_ctx; P.kv32 = L.kv32;
-    P.silu_tab = L.silu_tab; P.out_q = L.out_q;
+    P.n_tokens = L.n_tokens; P.tok0 = L.tok0; P.out_q = L.out_q;
     const int ng = L.w.M / 8;
     const int N = L.n_tokens;
     const bool prefill = N > 1;
+    // the (pro, epi) pairs instantiated here; PRO_ACTF is not one (Q4_0 callers quantize first)
+    const bool norm = pro == PRO_NORM && (epi == EPI_QKV || epi == EPI_SWIGLU || epi == EPI_STORE);
+    const bool actq = pro == PRO_ACTQ && (epi == EPI_STORE || epi == EPI_RESID);
+    if (!norm && !actq) return hipErrorNotSupported;
+    if (!mv_inputs_set(L, pro)) return hipErrorInvalidValue;
     switch (epi) {
         case EPI_QKV:
-            if (pro != PRO_NORM || ng % 4 || P.K > 8192) return hipErrorInvalidValue;
+            if (ng % 4 || P.K > 8192) return hipErrorInvalidValue;
             return prefill ? go<256, 4, 4, PRO_NORM, EPI_QKV, 2>(P, ng, N, s)
                            : go<256, 1, 4, PRO_NORM, EPI_QKV, 4>(P, ng, N, s);
         case EPI_SWIGLU:
-            if (pro != PRO_NORM || ng % 8 || P.K > 16384) return hipErrorInvalidValue;
+            if (ng % 8 || P.K > 16384) return hipErrorInvalidValue;
             return prefill ? go<512, 4, 4, PRO_NORM, EPI_SWIGLU, 2>(P, ng, N, s)
                            : go<512, 1, 4, PRO_NORM, EPI_SWIGLU, 4>(P, ng, N, s);
         case EPI_STORE:
@@ -464,11 +382,11 @@ hipError_t launch_matvec(const MvLaunch & L, int pro, int epi, hipStream_t s) {
             return prefill ? go<64, 4, 12, PRO_ACTQ, EPI_STORE, 2>(P, ng, N, s)
                            : go<64, 1, 12, PRO_ACTQ, EPI_STORE, 8>(P, ng, N, s);
         case EPI_RESID:
-            if (pro != PRO_ACTQ || P.nb > 12 * 64) return hipErrorInvalidValue;
+            if (P.nb > 12 * 64) return hipErrorInvalidValue;
             return prefill ? go<64, 4, 12, PRO_ACTQ, EPI_RESID, 2>(P, ng, N, s)
                            : go<64, 1, 12, PRO_ACTQ, EPI_RESID, 8>(P, ng, N, s);
     }
-    return hipErrorInvalidValue;
+    return hipErrorNotSupported;
 }
 
 }  // namespace lvk

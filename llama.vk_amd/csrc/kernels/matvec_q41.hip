@@ -25,24 +25,14 @@ namespace lvk {
 namespace {
 using namespace mv;
 
-struct P41 {
+struct Image41 {
     const uint4 * nib;
     const float4 * scl;       // [g][NC][2][64]: d, then m
     int M, K, nb, NC;
-    const float * x;
-    const float * g;
-    ActQ xq;
-    const StepParams * sp;
-    int n_tokens, tok0, out_tok0;
-    float * y;
-    uint16_t * q16;
-    uint16_t * kc;
-    uint16_t * vc;
-    const float2 * rope;
-    int n_embd, head_dim, n_ctx;
-    int kv32;                   // f32 KV cache and queries (f16_kv = false)
-    const uint16_t * silu_tab;
-    ActQ out_q;
+};
+struct P41 : Image41, MvArgs {
+    int n_tokens, tok0;       // the token window: rows tok0 .. tok0 + n_tokens - 1 of x / xq
+    ActQ out_q;               // EPI_SWIGLU: quantized u
 };
 
 // ---------------------------------------------------------------------------
@@ -93,16 +83,14 @@ __global__ __launch_bounds__(NT) void k_matvec_q41(P41 P) {
     if constexpr (PRO == PRO_NORM || PRO == PRO_ACTF) {
         const int nunits = K / 8;
         if constexpr (PRO == PRO_NORM) {
-            // ggml.c:6058-6076: float squares summed in double (RMSNorm order)
+            // the sum of squares per token (sumsq4), a wave tree, the NW wave sums in order
             for (int tt = 0; tt < T; ++tt) {
                 double acc = 0.0;
                 if (tt < nt) {
                     const float * xr = P.x + (size_t) (P.tok0 + t0 + tt) * K;
                     for (int u = tid; u < nunits; u += NT) {
-                        const float4 a = ((const float4 *) xr)[2 * u], b = ((const float4 *) xr)[2 * u + 1];
-                        const float e[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-#pragma unroll
-                        for (int q = 0; q < 8; ++q) { const float sq = e[q] * e[q]; acc += (double) sq; }
+                        sumsq4(acc, ((const float4 *) xr)[2 * u]);
+                        sumsq4(acc, ((const float4 *) xr)[2 * u + 1]);
                     }
                 }
                 acc = wave_sum_d(acc);
@@ -128,27 +116,11 @@ __global__ __launch_bounds__(NT) void k_matvec_q41(P41 P) {
             // whole quads stay together: nunits % 4 == 0 and NT % 4 == 0
             for (int u0 = 0; u0 < nunits; u0 += NT) {
                 const int u = min(u0 + tid, nunits - 1);
-                const float4 a = ((const float4 *) xr)[2 * u], b = ((const float4 *) xr)[2 * u + 1];
-                float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-                if constexpr (PRO == PRO_NORM) {
-                    const float4 ga = ((const float4 *) P.g)[2 * u], gb = ((const float4 *) P.g)[2 * u + 1];
-                    const float gg[8] = {ga.x, ga.y, ga.z, ga.w, gb.x, gb.y, gb.z, gb.w};
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        const float yn = v[e] * scale;      // ggml_vec_scale_f32 (ggml.c:6076)
-                        v[e] = gg[e] * yn;                  // ggml_mul(repeat(g), cur) (llama.cpp:984)
-                    }
-                }
-                float d, m;
-                uint32_t qw;
-                q41_quad(v, d, m, qw);
-                // gather the block's 4 qs words into every lane of the quad
-                uint32_t qs[4];
-                qs[0] = __builtin_bit_cast(uint32_t, quad_bcast<0>(__builtin_bit_cast(float, qw)));
-                qs[1] = __builtin_bit_cast(uint32_t, quad_bcast<1>(__builtin_bit_cast(float, qw)));
-                qs[2] = __builtin_bit_cast(uint32_t, quad_bcast<2>(__builtin_bit_cast(float, qw)));
-                qs[3] = __builtin_bit_cast(uint32_t, quad_bcast<3>(__builtin_bit_cast(float, qw)));
-                if (u0 + tid < nunits && (u & 3) == 0) act41_store(act, dyv, myv, ys, u >> 2, qs, d, m);
+                float v[8];
+                unit_vals(((const float4 *) xr)[2 * u], ((const float4 *) xr)[2 * u + 1], v);
+                if constexpr (PRO == PRO_NORM)
+                    pro_norm_unit<PRO>(v, ((const float4 *) P.g)[2 * u], ((const float4 *) P.g)[2 * u + 1], scale);
+                q41_unit_store(v, u, u0 + tid < nunits, act, dyv, myv, ys);
             }
         }
     } else {
@@ -158,12 +130,9 @@ __global__ __launch_bounds__(NT) void k_matvec_q41(P41 P) {
             float * dyv = dyv_base + (size_t) tt * NC * 32;
             float * myv = myv_base + (size_t) tt * NC * 32;
             float * ys = ys_base + (size_t) tt * nb * 4;
-            for (int b = tid; b < nb; b += NT) {
-                const uint4 q4 = P.xq.qs[(size_t) t * P.xq.nb + b];
-                const uint32_t qs[4] = {q4.x, q4.y, q4.z, q4.w};
-                act41_store(act, dyv, myv, ys, b, qs, P.xq.d[(size_t) t * P.xq.nb + b],
-                            P.xq.m[(size_t) t * P.xq.nb + b]);
-            }
+            for (int b = tid; b < nb; b += NT)
+                q41_block_store(act, dyv, myv, ys, b, P.xq.qs[(size_t) t * P.xq.nb + b], P.xq.d[(size_t) t * P.xq.nb + b],
+                                P.xq.m[(size_t) t * P.xq.nb + b]);
         }
     }
     __syncthreads();
@@ -260,41 +229,8 @@ __global__ __launch_bounds__(NT) void k_matvec_q41(P41 P) {
         const float o = off[tt] * 32.0f;        // acc_offset * QK (ggml.c:2249)
         res[tt] = h + o;
     }
-    if constexpr (EPI == EPI_STORE) {
-#pragma unroll
-        for (int tt = 0; tt < T; ++tt)
-            if (tt < nt && j == 0) P.y[(size_t) (P.out_tok0 + t0 + tt) * P.M + row] = res[tt];
-    } else if constexpr (EPI == EPI_RESID) {
-#pragma unroll
-        for (int tt = 0; tt < T; ++tt)
-            if (tt < nt && j == 0) {
-                float * yp = P.y + (size_t) (P.out_tok0 + t0 + tt) * P.M + row;
-                *yp = res[tt] + *yp;                 // ggml_add(cur, inpSA) (llama.cpp:1071,1103)
-            }
-    } else if constexpr (EPI == EPI_QKV) {
-        const int E = P.n_embd, hd = P.head_dim;
-        const int which = row / E;
-        const int e = row - which * E;
-        const int n_past = P.sp->n_past;
-#pragma unroll
-        for (int tt = 0; tt < T; ++tt) {
-            const float other_r = __shfl_xor(res[tt], 8);
-            if (tt < nt && j == 0) {
-                const int pos = n_past + t0 + tt;
-                if (which < 2) {
-                    // ggml_compute_forward_rope_f32 mode 0 (ggml.c:7209-7223)
-                    const int i0 = e % hd;
-                    const float2 cs = P.rope[(size_t) pos * (hd / 2) + (i0 >> 1)];
-                    float out;
-                    if ((i0 & 1) == 0) { const float a = res[tt] * cs.x, b = other_r * cs.y; out = a - b; }
-                    else               { const float a = other_r * cs.y, b = res[tt] * cs.x; out = a + b; }
-                    if (which == 0) kv_store(P.q16, (size_t) (t0 + tt) * E + e, out, P.kv32);
-                    else            kv_store(P.kc, (size_t) pos * E + e, out, P.kv32);
-                } else {
-                    kv_store(P.vc, (size_t) e * P.n_ctx + pos, res[tt], P.kv32);
-                }
-            }
-        }
+    if constexpr (EPI != EPI_SWIGLU) {
+        mv_epilogue_rows<T, EPI>(P, res, row, j, P.M, t0, nt);
     } else if constexpr (EPI == EPI_SWIGLU) {
         // WG = 8 waves = rows [64b, 64b+64) of the fused W1|W3 image (interleaved
         // per 4 rows): wave k rows 0-3 are w1 rows 32b+4k..+3, rows 4-7 the w3 rows
@@ -310,8 +246,7 @@ __global__ __launch_bounds__(NT) void k_matvec_q41(P41 P) {
             if (tt < nt) {
                 const float a1 = ures[tt * 64 + (e >> 2) * 8 + (e & 3)];        // w1 x
                 const float a3 = ures[tt * 64 + (e >> 2) * 8 + 4 + (e & 3)];    // w3 x
-                const float sl = f16_to_f32(P.silu_tab[f32_to_f16(a1)]);   // ggml_vec_silu_f32 (ggml.c:2495)
-                ub[tt * 32 + e] = sl * a3;                                  // ggml_mul (llama.cpp:1096)
+                ub[tt * 32 + e] = silu_mul(a1, a3, P.silu_tab);
             }
         }
         __syncthreads();
@@ -321,7 +256,7 @@ __global__ __launch_bounds__(NT) void k_matvec_q41(P41 P) {
                 float d, m;
                 uint32_t qw;
                 q41_block_lds(ub + tt * 32, k, d, m, qw);
-                const int t = P.out_tok0 + t0 + tt;
+                const int t = t0 + tt;
                 const int blk = blockIdx.x;
                 ((uint32_t *) (P.out_q.qs + (size_t) t * P.out_q.nb + blk))[k] = qw;
                 if (k == 0) {
@@ -358,26 +293,27 @@ hipError_t dispatch41(const P41 & P, int pro, int epi, int ng, int N, hipStream_
             if (pro == PRO_ACTQ) return go41<NT, T, PRO_ACTQ, EPI_RESID, D>(P, ng, N, s);
             break;
     }
-    return hipErrorInvalidValue;
+    return hipErrorNotSupported;
 }
 
 }  // namespace
 
 hipError_t launch_matvec_q41(const MvLaunch & L, int pro, int epi, hipStream_t s) {
     if (L.w.M % 8 || L.w.K % 256) return hipErrorInvalidValue;
+    if (epi == EPI_SWIGLU ? pro != PRO_NORM
+                          : !(epi == EPI_STORE || (epi == EPI_QKV && pro == PRO_NORM) || (epi == EPI_RESID && pro == PRO_ACTQ)))
+        return hipErrorNotSupported;
+    if (!mv_inputs_set(L, pro)) return hipErrorInvalidValue;
     P41 P{};
+    mv_fill(P, L, false);
     P.nib = L.w.nib;
     P.scl = (const float4 *) L.w.scl;
     P.M = L.w.M; P.K = L.w.K; P.nb = L.w.K / 32; P.NC = (P.nb + 31) / 32;
-    P.x = L.x; P.g = L.g; P.xq = L.xq; P.sp = L.sp;
-    P.n_tokens = L.n_tokens; P.tok0 = L.tok0; P.out_tok0 = L.out_tok0;
-    P.y = L.y; P.q16 = L.q16; P.kc = L.kc; P.vc = L.vc; P.rope = L.rope.cs;
-    P.n_embd = L.n_embd; P.head_dim = L.head_dim; P.n_ctx = L.n_ctx; P.kv32 = L.kv32;
-    P.silu_tab = L.silu_tab; P.out_q = L.out_q;
+    P.n_tokens = L.n_tokens; P.tok0 = L.tok0; P.out_q = L.out_q;
     const int ng = L.w.M / 8;
     const int N = L.n_tokens;
     if (epi == EPI_SWIGLU) {
-        if (pro != PRO_NORM || ng % 8) return hipErrorInvalidValue;
+        if (ng % 8) return hipErrorInvalidValue;
         return N > 1 ? go41<512, 2, PRO_NORM, EPI_SWIGLU, 2>(P, ng, N, s)
                      : go41<512, 1, PRO_NORM, EPI_SWIGLU, 2>(P, ng, N, s);
     }

@@ -237,16 +237,6 @@ static double qbytes(const QMatrix & w) {
     return (double) w.M * (w.K / 32) * (w.qtype == Q4_0 ? 20 : 24);
 }
 
-// decode kernels: the CU-balanced path (matvec_cu.hip) where its row length is
-// compiled in, else the generic kernel
-static hipError_t mv_launch(const MvLaunch & L, int pro, int epi, hipStream_t s) {
-    if (L.n_tokens == 1 && matvec_cu_supported(L.w.K, L.w.qtype)) {
-        const hipError_t e = launch_matvec_cu(L, pro, epi, s);
-        if (e != hipErrorNotSupported) return e;
-    }
-    return launch_matvec(L, pro, epi, s);
-}
-
 // batches go through the batched matmuls (launch_act + launch_mm) when every matrix of the
 // model fits them: f16 weights from 2 tokens on (their matvec is single-token only), the Q4
 // types from 16 (the MFMA tile is 16 tokens wide; below that the per-row VALU kernels win)
@@ -346,7 +336,7 @@ void Context::enqueue_forward(int n, bool last_only, const int * tok_src, int lo
         a.w = ly.wqkv; a.x = x; a.g = ly.attn_norm; a.sp = sp_d; a.n_tokens = n;
         a.q16 = q16; a.kc = kcl; a.vc = vcl; a.rope.cs = rope;
         a.n_embd = E; a.head_dim = hd; a.n_ctx = n_ctx; a.kv32 = kv32;
-        timed_launch(K_QKV, qbytes(ly.wqkv), [&] { return mv_launch(a, PRO_NORM, EPI_QKV, stream); });
+        timed_launch(K_QKV, qbytes(ly.wqkv), [&] { return launch_matvec_auto(a, PRO_NORM, EPI_QKV, stream); });
         if (prompt_attn)
             timed_launch(K_ATTN, 0, [&] { return launch_attention_prompt(at, (uint16_t *) scores, ActImage{}, stream); });
         else if (decode_attn)
@@ -355,7 +345,7 @@ void Context::enqueue_forward(int n, bool last_only, const int * tok_src, int lo
             timed_launch(K_ATTN, 0, [&] { return launch_attention(at, stream); });
         MvLaunch b;      // input: the attention's f32 rows (f16 weights) or its quantized blocks
         b.w = ly.wo; b.x = attn_f32; b.xq = aq_attn; b.y = x; b.sp = sp_d; b.n_tokens = n;
-        timed_launch(K_WO, qbytes(ly.wo), [&] { return mv_launch(b, attn_f32 ? PRO_ACTF : PRO_ACTQ, EPI_RESID, stream); });
+        timed_launch(K_WO, qbytes(ly.wo), [&] { return launch_matvec_auto(b, attn_f32 ? PRO_ACTF : PRO_ACTQ, EPI_RESID, stream); });
         MvLaunch c;
         c.w = ly.w13; c.x = x; c.g = ly.ffn_norm; c.sp = sp_d; c.n_tokens = n; c.silu_tab = silu_tab;
         c.out_q = aq_ffn; c.u = u_ffn;
@@ -379,7 +369,7 @@ void Context::enqueue_forward(int n, bool last_only, const int * tok_src, int lo
         o.w = model.output; o.x = x; o.g = model.norm; o.sp = sp_d; o.y = logits_out;
         o.tok0 = last_only ? n - 1 : 0;
         o.n_tokens = last_only ? 1 : n;
-        timed_launch(K_LMHEAD, qbytes(model.output), [&] { return mv_launch(o, PRO_NORM, EPI_STORE, stream); });
+        timed_launch(K_LMHEAD, qbytes(model.output), [&] { return launch_matvec_auto(o, PRO_NORM, EPI_STORE, stream); });
     }
     if (want_embedding)
         LVK_HIP(launch_rmsnorm_rows(x + (size_t) (n - 1) * E, model.norm, E, 1, emb_d, stream));

@@ -97,25 +97,12 @@ static int mul_mat_impl(int type, const void * w, int m, int k, const float * g,
     lvk::MvLaunch L;
     L.w = q; L.sp = spd; L.n_tokens = n; L.y = yd;
     float * xd = dv.up(x, (size_t) n * k);
-    if (type == lvk::Q4_1) {
-        // Q4_1 kernels quantize the f32 input in their prologue
+    if (type == lvk::Q4_1 || norm || (n == 1 && lvk::matvec_cu_supported(k, type))) {
+        // the kernel quantizes the f32 input in its prologue: every Q4_1 kernel, the Q4_0 norm
+        // kernels, and the Q4_0 single-column decode kernel (matvec_cu.hip) where compiled in
         L.x = xd;
         if (norm) L.g = dv.up(g, (size_t) k);
-        const int pro = norm ? lvk::PRO_NORM : lvk::PRO_ACTF;
-        // single column: the CU-balanced decode kernel (matvec_cu41.hip) where compiled in
-        hipError_t e = hipErrorNotSupported;
-        if (n == 1 && lvk::matvec_cu_supported(k, lvk::Q4_1)) e = lvk::launch_matvec_cu(L, pro, lvk::EPI_STORE, nullptr);
-        if (e == hipErrorNotSupported) e = lvk::launch_matvec(L, pro, lvk::EPI_STORE, nullptr);
-        LVK_HIP(e);
-    } else if (n == 1 && lvk::matvec_cu_supported(k)) {
-        // single column: the decode kernel (matvec_cu.hip), quantizing in its prologue
-        L.x = xd;
-        if (norm) L.g = dv.up(g, (size_t) k);
-        LVK_HIP(lvk::launch_matvec_cu(L, norm ? lvk::PRO_NORM : lvk::PRO_ACTF, lvk::EPI_STORE, nullptr));
-    } else if (norm) {
-        L.x = xd;
-        L.g = dv.up(g, (size_t) k);
-        LVK_HIP(lvk::launch_matvec(L, lvk::PRO_NORM, lvk::EPI_STORE, nullptr));
+        LVK_HIP(lvk::launch_matvec_auto(L, norm ? lvk::PRO_NORM : lvk::PRO_ACTF, lvk::EPI_STORE, nullptr));
     } else {
         lvk::ActQ a;
         a.nb = (int) nb;
