@@ -22,7 +22,7 @@
 // (t0+t1)+(t2+t3); leftovers are added in double.  Here the 4 registers r of a
 // dot are the 4 lanes of a quad (16-byte loads), so loads are contiguous and
 // the reduce is a fixed DPP pattern.
-#include "lvk_device.h"
+#include "attention_common.h"
 #include "lvk_kernels.h"
 #include "matvec_common.h"
 
@@ -30,45 +30,12 @@ namespace lvk {
 
 namespace {
 
-#ifdef LVK_PROBE_TIMING   // dev probe builds only: per-wave s_memtime trace of the attention kernel
-__device__ unsigned long long g_atrace[64 * 4 * 16];
-#define LVK_AT(ev)                                                                                    \
-    do {                                                                                              \
-        const unsigned long long t_ = __builtin_amdgcn_s_memtime();                                   \
-        if ((threadIdx.x & 63) == 0 && blockIdx.y == 0)                                               \
-            g_atrace[((blockIdx.x * 2 + blockIdx.z) & 63) * 64 + (threadIdx.x >> 6) * 16 + (ev)] = t_; \
-    } while (0)
-#else
-#define LVK_AT(ev) do { } while (0)
-#endif
-
-__device__ __forceinline__ void unpack8h(const uint4 v, float f[8]) {
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        f[2 * k] = f16_to_f32((uint16_t) (w[k] & 0xFFFFu));
-        f[2 * k + 1] = f16_to_f32((uint16_t) (w[k] >> 16));
-    }
-}
+constexpr int HD = ATTN_HD;
 
 // one 1 KiB LDS-DMA piece per wave: lane l moves 16 bytes from src to
 // lds + 16*l (global_load_lds_dwordx4, no VGPR destination)
 __device__ __forceinline__ void dma16(const void * src, uint8_t * lds) {
     __builtin_amdgcn_global_load_lds((const void *) src, (__attribute__((address_space(3))) void *) lds, 16, 0, 0);
-}
-
-// reduce the quad's 4x8 accumulators in the AVX2 F32Cx8_REDUCE order
-__device__ __forceinline__ float quad_f16dot_reduce(const float s[8]) {
-    float S[8];
-#pragma unroll
-    for (int l = 0; l < 8; ++l) {
-        const float v0 = quad_bcast<0>(s[l]), v1 = quad_bcast<1>(s[l]);
-        const float v2 = quad_bcast<2>(s[l]), v3 = quad_bcast<3>(s[l]);
-        const float a = v0 + v1, b = v2 + v3;     // x[0]+=x[1]; x[2]+=x[3]
-        S[l] = a + b;                              // x[0]+=x[2]
-    }
-    const float t0 = S[0] + S[4], t1 = S[1] + S[5], t2 = S[2] + S[6], t3 = S[3] + S[7];
-    return (t0 + t1) + (t2 + t3);                  // hadd, hadd
 }
 
 // table_exp_f16[h] (ggml.c:2915-2927: fp16(expf(fp16->f32(h)))) for the
@@ -118,7 +85,16 @@ __device__ __forceinline__ void unpack8(const Vec8<F32> & v, float f[8]) {
     }
 }
 
-template <int HD, int QT, bool F32>
+// The F32Cx8 reduce of a quad's accumulators.  F32 keeps the broadcast form of the quad sums:
+// with the butterflies hipcc allocates 256 instead of 179 VGPRs for that instantiation, and the
+// attention of a 200-token 7B prompt on the f32 KV cache measured 6.4 against 3.5 ms
+// (profiles/attn_pieces_kernel_resources.md)
+template <bool F32>
+__device__ __forceinline__ float dot_reduce(const float (&s)[8]) {
+    return F32 ? quad_reduce_bcast(s) : quad_reduce(s);
+}
+
+template <int QT, bool F32>
 __global__ __launch_bounds__(256) void k_attn(const uint16_t * __restrict__ q16, const uint16_t * __restrict__ kc,
                                               const uint16_t * __restrict__ vc, const uint16_t * __restrict__ exp_tab,
                                               ActQ out, const StepParams * sp, int E, int n_ctx, float scale,
@@ -130,7 +106,7 @@ __global__ __launch_bounds__(256) void k_attn(const uint16_t * __restrict__ q16,
     const int n_kv = n_past + N;
     const int h = blockIdx.x, t = blockIdx.y, half = blockIdx.z;
     if (t >= N) return;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = tid & 3;
+    const int tid = threadIdx.x, lane = tid & 63, r = tid & 3;
     float * sc = (float *) smem;                                   // n_ctx scores / exp values
     uint16_t * p16 = (uint16_t *) (smem + (size_t) n_ctx * 4);     // n_ctx f16 probabilities
     float * red = (float *) (smem + (size_t) n_ctx * 6);           // 8 floats
@@ -165,7 +141,6 @@ __global__ __launch_bounds__(256) void k_attn(const uint16_t * __restrict__ q16,
     // V steps 0..VS-1 go to LDS by DMA: step s of the workgroup's 64 dims is VSB bytes at
     // vlds + s*VSB, thread tid's first 16 bytes at + tid*16 (f32: the second at + 4096 + tid*16)
     uint8_t * vlds = smem + (size_t) n_ctx * 6 + 64;
-    LVK_AT(0);
     load_k(0);
     {
         uint8_t * vl = vlds + (tid & ~63) * 16;       // wave-uniform base
@@ -180,7 +155,6 @@ __global__ __launch_bounds__(256) void k_attn(const uint16_t * __restrict__ q16,
             }
         }
     }
-    LVK_AT(1);
 
     // ---- phase 1: KQ (ggml_vec_dot_f16 over HD, Q in f16) ----
     for (int pb = 0; pb < npos; pb += PB) {
@@ -197,28 +171,22 @@ __global__ __launch_bounds__(256) void k_attn(const uint16_t * __restrict__ q16,
 #pragma unroll
                     for (int l = 0; l < 8; ++l) s[l] = __builtin_fmaf(kf[l], qf[l], s[l]);
                 }
-                const float kq = quad_f16dot_reduce(s);
+                const float kq = dot_reduce<F32>(s);
                 const int pp = pb + ps * 64 + (tid >> 2);
                 if (r == 0 && pp < npos) sc[pp] = kq * scale;      // ggml_vec_scale_f32 (llama.cpp:1026)
             }
         }
     }
-    LVK_AT(2);
     for (int p = npos + tid; p < n_kv; p += 256) sc[p] = -INFINITY;   // ggml.c:7028-7031
     __syncthreads();
     if (scores_dbg && half == 0)
         for (int p = tid; p < n_kv; p += 256) scores_dbg[((size_t) t * gridDim.x + h) * n_ctx + p] = sc[p];
 
     // ---- phase 2: softmax (ggml.c:7099-7121) ----
+    auto bar = [] { __syncthreads(); };
     float mx = -INFINITY;
     for (int p = tid; p < n_kv; p += 256) { const float v = sc[p]; mx = v > mx ? v : mx; }
-    mx = wave_max_f(mx);
-    if (lane == 0) red[wave] = mx;
-    __syncthreads();
-    {
-        const float a = red[0] > red[1] ? red[0] : red[1], b = red[2] > red[3] ? red[2] : red[3];
-        mx = a > b ? a : b;
-    }
+    mx = wg_max_f(mx, red, bar);
     double sum = 0.0;   // exact in any order: every term is an fp16 value in [0,1]
     for (int p = tid; p < n_kv; p += 256) {
         const float v = sc[p];
@@ -229,10 +197,7 @@ __global__ __launch_bounds__(256) void k_attn(const uint16_t * __restrict__ q16,
         }
         sc[p] = e;
     }
-    sum = wave_sum_d(sum);     // any order: the sum is exact
-    if (lane == 0) redd[wave] = sum;
-    __syncthreads();
-    sum = (redd[0] + redd[1]) + (redd[2] + redd[3]);
+    sum = wg_sum_d(sum, redd, bar);
     const float scl = (float) (1.0 / sum);
     const int n_pad = (n_kv + 31) & ~31;
     if constexpr (F32) {
@@ -244,7 +209,6 @@ __global__ __launch_bounds__(256) void k_attn(const uint16_t * __restrict__ q16,
     if (!F32 && p16_out && half == 0)
         for (int p = tid; p < n_kv; p += 256) p16_out[((size_t) t * gridDim.x + h) * n_ctx + p] = p16[p];
 
-    LVK_AT(3);
     // ---- phase 3: KQV = ggml_vec_dot_f16(n_kv, V row, P) ----
     __syncthreads();     // vmcnt(0) + barrier: every wave's V DMA has landed
     const int nsteps = min(np, lim + 1 + 31) / 32;     // steps holding at least one unmasked position
@@ -269,7 +233,7 @@ __global__ __launch_bounds__(256) void k_attn(const uint16_t * __restrict__ q16,
         pv_step(v8, st);
     }
     for (int st = VS; st < nsteps; ++st) pv_step(ld8<F32>(vc, vrow + (size_t) st * 32 + r * 8), st);
-    const float res = quad_f16dot_reduce(s);
+    const float res = dot_reduce<F32>(s);
     float o = res;
     if (F32 && np < n_kv && np <= lim) {
         // leftovers in float, in position order (ggml.c:1736-1739: sumf += x[i]*y[i])
@@ -309,32 +273,17 @@ __global__ __launch_bounds__(256) void k_attn(const uint16_t * __restrict__ q16,
     }
     if (r == 0 && out_f32) out_f32[(size_t) t * E + h * HD + d] = o;
 
-    LVK_AT(4);
     // ---- phase 4: quantize HD/2 outputs = HD/64 weight blocks ----
     __syncthreads();
     float * ob = sc;
     if (r == 0) ob[tid >> 2] = o;
     __syncthreads();
-    if (tid < HD / 2) {
-        const float v = ob[tid];
-        const int blk = (h * HD + half * (HD / 2)) / 32 + (tid >> 5);
-        uint32_t * scratch = (uint32_t *) (sc + 128) + (tid >> 5) * 4;
-        if constexpr (QT == Q4_0) {
-            float amax = fabsf(v);
-            for (int o2 = 16; o2 > 0; o2 >>= 1) { const float w = __shfl_xor(amax, o2); amax = w > amax ? w : amax; }
-            const float dd = amax / 7.0f;
-            const float id = (amax != 0.0f) ? 7.0f / amax : 0.0f;
-            const uint32_t qq = (uint32_t) ((int) __builtin_rintf(v * id) + 8) & 15u;
-            uint32_t part = qq << (4 * (lane & 7));
-            part |= __shfl_xor(part, 1);
-            part |= __shfl_xor(part, 2);
-            part |= __shfl_xor(part, 4);
-            if ((lane & 7) == 0) scratch[(lane & 31) >> 3] = part;
-            __builtin_amdgcn_wave_barrier();
-            if ((lane & 31) == 0) {
-                out.d[(size_t) t * out.nb + blk] = dd;
-                out.qs[(size_t) t * out.nb + blk] = make_uint4(scratch[0], scratch[1], scratch[2], scratch[3]);
-            }
+    if constexpr (QT == Q4_0) {
+        if (tid < HD / 2) {      // wave 0: a 32-lane half per block
+            float dd;
+            uint4 qs;
+            mv::q40_block32(ob[tid], lane, dd, qs);
+            if ((lane & 31) == 0) mv::actq_store_block(out, t, (h * HD + half * (HD / 2)) / 32 + (tid >> 5), dd, qs);
         }
     }
     if constexpr (QT == Q4_1) {
@@ -345,21 +294,12 @@ __global__ __launch_bounds__(256) void k_attn(const uint16_t * __restrict__ q16,
             float dd, mm;
             uint32_t qw;
             mv::q41_block_lds(ob + bb * 32, k, dd, mm, qw);
-            ((uint32_t *) (out.qs + (size_t) t * out.nb + blk))[k] = qw;
-            if (k == 0) {
-                out.d[(size_t) t * out.nb + blk] = dd;
-                out.m[(size_t) t * out.nb + blk] = mm;
-            }
+            mv::actq_store_block41(out, t, blk, k, dd, mm, qw);
         }
     }
-    LVK_AT(5);
 }
 
 }  // namespace
-
-#ifdef LVK_PROBE_TIMING
-void * lvk_probe_atrace() { void * p = nullptr; (void) hipGetSymbolAddress(&p, HIP_SYMBOL(g_atrace)); return p; }
-#endif
 
 hipError_t exp_check(const uint16_t * exp_tab, int * bad_d, hipStream_t s) {
     hipError_t e = hipMemsetAsync(bad_d, 0, 2 * sizeof(int), s);
@@ -369,16 +309,15 @@ hipError_t exp_check(const uint16_t * exp_tab, int * bad_d, hipStream_t s) {
 }
 
 hipError_t launch_attention(const AttnLaunch & A, hipStream_t s) {
-    const int hd = A.n_embd / A.n_head;
-    if (hd != 128 || A.n_ctx % 32 || A.n_ctx < 128) return hipErrorInvalidValue;
+    if (A.n_embd / A.n_head != HD || A.n_ctx % 32 || A.n_ctx < 128) return hipErrorInvalidValue;
     if (A.kv32 && A.p16_out) return hipErrorInvalidValue;
     if (A.out_qtype != Q4_0 && A.out_qtype != Q4_1) return hipErrorNotSupported;
-    const float scale = 1.0f / sqrtf((float) A.n_embd / (float) A.n_head);   // llama.cpp:1028
+    const float scale = attn_scale(A.n_embd, A.n_head);
     dim3 grid(A.n_head, A.n_tokens, 2);
     // scores, P16, reductions, then V steps 0..15 by DMA (4 KiB each)
     const size_t lds = (size_t) A.n_ctx * 6 + 64 + 16 * 4096;
 #define LVK_ATTN_GO(QT_, F32_)                                                                                  \
-    LVK_LAUNCH((k_attn<128, QT_, F32_>), grid, dim3(256), lds, s, A.q16, A.kc, A.vc, A.exp_tab, A.out, A.sp,  \
+    LVK_LAUNCH((k_attn<QT_, F32_>), grid, dim3(256), lds, s, A.q16, A.kc, A.vc, A.exp_tab, A.out, A.sp,  \
                A.n_embd, A.n_ctx, scale, A.scores, A.out_f32, A.p16_out, A.exp_computed)
     if (A.out_qtype == Q4_1) {
         if (A.kv32) LVK_ATTN_GO(Q4_1, true); else LVK_ATTN_GO(Q4_1, false);

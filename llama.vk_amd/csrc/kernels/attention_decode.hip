@@ -1,7 +1,6 @@
 // attention_decode.hip -- single-token (decode) attention over the f16 KV
-// cache, bit-faithful to the reference graph (llama.cpp:1010-1061) like
-// attention.hip, split so that the KV bytes of a layer are read by 4x as many
-// CUs in ONE launch.
+// cache, bit-faithful to the reference graph (llama.cpp:1010-1061), split so
+// that the KV bytes of a layer are read by 4x as many CUs in ONE launch.
 //
 // A decode step reads 2 * n_kv * 256 B of K and V per head; one workgroup per
 // head pulls ~100 KB through one CU at ~17 B/cycle.  Here 4 workgroups share a
@@ -22,7 +21,7 @@
 // Every workgroup of a launch is resident at once (4 H <= 1024 workgroups of
 // <= 42 KB LDS), which the exchange needs; every spin is bounded so a violated
 // assumption cannot hang the GPU.
-#include "lvk_device.h"
+#include "attention_common.h"
 #include "lvk_kernels.h"
 #include "matvec_common.h"
 
@@ -33,31 +32,7 @@ namespace lvk {
 
 namespace {
 
-constexpr int HD = 128;
-
-__device__ __forceinline__ void unpack8(const uint4 v, float f[8]) {
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        f[2 * k] = f16_to_f32((uint16_t) (w[k] & 0xFFFFu));
-        f[2 * k + 1] = f16_to_f32((uint16_t) (w[k] >> 16));
-    }
-}
-
-// the quad's 4 x 8 accumulators in the AVX2 F32Cx8_REDUCE order (as attention.hip)
-__device__ __forceinline__ float quad_reduce(const float s[8]) {
-    float S[8];
-#pragma unroll
-    for (int l = 0; l < 8; ++l) {
-        const float v0 = quad_bcast<0>(s[l]), v1 = quad_bcast<1>(s[l]);
-        const float v2 = quad_bcast<2>(s[l]), v3 = quad_bcast<3>(s[l]);
-        const float a = v0 + v1, b = v2 + v3;
-        S[l] = a + b;
-    }
-    const float t0 = S[0] + S[4], t1 = S[1] + S[5], t2 = S[2] + S[6], t3 = S[3] + S[7];
-    return (t0 + t1) + (t2 + t3);
-}
-
+constexpr int HD = ATTN_HD;
 
 // a workgroup barrier for LDS hand-offs only: __syncthreads() also drains vmcnt, which
 // would make every wave with V rows in flight wait for them
@@ -111,20 +86,19 @@ struct AttnDArgs {
     unsigned epoch;
     ActQ out;
     float * out_f32;
-    int exp_mode;
     unsigned * err;               // host-mapped error word (nullptr: none)
     int short_max;                // n_kv <= short_max: no score exchange (every workgroup scores all)
     int seq_epochs;               // epoch += sp->seq << 7 (granules never zeroed between tokens)
 };
 
-// The 4 workgroups of a head either split the scores and exchange them as granules, or
-// (n_kv <= A.short_max, DYN) every workgroup scores all positions itself (4x the K reads,
-// from the XCD's L2).  !DYN: always the exchange.  EM: the exp mode compiled in (exp_f16;
-// -1 reads A.exp_mode) -- a runtime mode puts the table path's load, and its vmcnt wait,
-// into the softmax loop.
-template <int QT, int EM, bool DYN = true>
-__device__ __forceinline__ void attn_d_run(const AttnDArgs & A, const int h, const int sl, uint8_t * smem,
-                                           const int tid) {
+// The 4 workgroups (h, sl) of a head either split the scores and exchange them as granules, or
+// (n_kv <= A.short_max) every workgroup scores all positions itself (4x the K reads, from the
+// XCD's L2).  EM: the exp mode compiled in (lvk_device.h exp_softmax) -- a runtime mode puts
+// the table path's load, and its vmcnt wait, into the softmax loop.
+template <int QT, int EM>
+__global__ __launch_bounds__(256) void k_attn_d(AttnDArgs A) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const int h = blockIdx.x, sl = blockIdx.y, tid = threadIdx.x;
     const int E = A.E, n_ctx = A.n_ctx, d0 = h * HD + sl * 32;
     const int lane = tid & 63, wave = tid >> 6, r = tid & 3;
     const int VS = n_ctx + 32;                                   // V row stride (halves): rows 16 banks apart
@@ -175,7 +149,7 @@ __device__ __forceinline__ void attn_d_run(const AttnDArgs & A, const int h, con
     const int n_kv = n_past + 1;
     const int n_pad = (n_kv + 31) & ~31;
     const int np = n_kv & ~31;
-    const bool exch = DYN ? n_kv > A.short_max : true;
+    const bool exch = n_kv > A.short_max;
     const int cs = exch ? 256 : 64;                     // position stride of this workgroup's chunks
     const int cb = exch ? sl * 64 : 0;                  // its first chunk
     // this workgroup's first two K chunks, issued once n_past is known.  (A speculative load
@@ -196,17 +170,17 @@ __device__ __forceinline__ void attn_d_run(const AttnDArgs & A, const int h, con
     {
         float qf[4][8];
 #pragma unroll
-        for (int st = 0; st < 4; ++st) unpack8(qv[st], qf[st]);
+        for (int st = 0; st < 4; ++st) unpack8h(qv[st], qf[st]);
         auto score = [&](const uint4 (&k4)[4], int p) {
             float s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
             for (int st = 0; st < 4; ++st) {
                 float kf[8];
-                unpack8(k4[st], kf);
+                unpack8h(k4[st], kf);
 #pragma unroll
                 for (int l = 0; l < 8; ++l) s[l] = __builtin_fmaf(kf[l], qf[st][l], s[l]);
             }
-            const float kq = quad_reduce(s);
+            const float kq = quad_reduce_bcast(s);     // not the butterflies: attention_common.h
             if (r == 0 && p < n_kv) {
                 const float v = kq * A.scale;                    // ggml_vec_scale_f32 (llama.cpp:1026)
                 if (!exch) sc[p] = v;
@@ -262,25 +236,14 @@ __device__ __forceinline__ void attn_d_run(const AttnDArgs & A, const int h, con
         }
     }
     LVK_DT(3);
-    mx = wave_max_f(mx);
-    if (lane == 0) red[wave] = mx;
-    bar();
-    LVK_DT(8);
-    {
-        const float a = red[0] > red[1] ? red[0] : red[1], b = red[2] > red[3] ? red[2] : red[3];
-        mx = a > b ? a : b;
-    }
+    mx = wg_max_f(mx, red, [&]() __attribute__((always_inline)) { lds_barrier(); LVK_DT(8); });
     double sum = 0.0;    // exact in any order: every term is an fp16 value in [0,1]
     for (int p = tid; p < n_kv; p += 256) {
-        const float e = f16_to_f32(exp_softmax<EM>(f32_to_f16(sc[p] - mx), A.exp_tab, A.exp_mode));
+        const float e = f16_to_f32(exp_softmax<EM>(f32_to_f16(sc[p] - mx), A.exp_tab));
         sum += (double) e;
         sc[p] = e;
     }
-    sum = wave_sum_d(sum);
-    if (lane == 0) redd[wave] = sum;
-    bar();
-    LVK_DT(9);
-    sum = (redd[0] + redd[1]) + (redd[2] + redd[3]);
+    sum = wg_sum_d(sum, redd, [&]() __attribute__((always_inline)) { lds_barrier(); LVK_DT(9); });
     const float scl = (float) (1.0 / sum);
     for (int p = tid; p < n_pad; p += 256) pl[p] = p < n_kv ? f32_to_f16(sc[p] * scl) : (uint16_t) 0;
     LVK_DT(4);
@@ -288,47 +251,6 @@ __device__ __forceinline__ void attn_d_run(const AttnDArgs & A, const int h, con
     bar();                    // the V DMA has landed too
     LVK_DT(5);
 
-#ifdef LVK_ATTN_PV_QUAD   // probe A/B only: the round-2 P.V (a lane quad per dim on waves 0-1)
-    float o = 0.0f;
-    const int q = tid >> 2;
-    const uint16_t * vr = vl + (size_t) q * VS;
-    if (tid < 128) {
-        float s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        const int ns = np / 32;
-        int st = 0;
-        for (; st + 2 <= ns; st += 2) {
-            const uint4 v0 = *((const uint4 *) (vr + st * 32) + r), p0 = *((const uint4 *) (pl + st * 32) + r);
-            const uint4 v1 = *((const uint4 *) (vr + st * 32 + 32) + r), p1 = *((const uint4 *) (pl + st * 32 + 32) + r);
-            float vf[8], pf[8];
-            unpack8(v0, vf);
-            unpack8(p0, pf);
-#pragma unroll
-            for (int l = 0; l < 8; ++l) s[l] = __builtin_fmaf(vf[l], pf[l], s[l]);
-            unpack8(v1, vf);
-            unpack8(p1, pf);
-#pragma unroll
-            for (int l = 0; l < 8; ++l) s[l] = __builtin_fmaf(vf[l], pf[l], s[l]);
-        }
-        if (st < ns) {
-            float vf[8], pf[8];
-            unpack8(*((const uint4 *) (vr + st * 32) + r), vf);
-            unpack8(*((const uint4 *) (pl + st * 32) + r), pf);
-#pragma unroll
-            for (int l = 0; l < 8; ++l) s[l] = __builtin_fmaf(vf[l], pf[l], s[l]);
-        }
-        const float res = quad_reduce(s);
-        o = res;
-        if (np < n_kv) {
-            double sumf = (double) res;
-            for (int p = np; p < n_kv; ++p) {
-                const float prod = f16_to_f32(vr[p]) * f16_to_f32(pl[p]);
-                sumf += (double) prod;
-            }
-            o = (float) sumf;
-        }
-    }
-#define LVK_OB_LANE (tid < 128 && r == 0)
-#else
     // P.V (ggml_vec_dot_f16, ggml.c:1781-1815): 8 threads per dim (wave w: dims 8w..8w+7),
     // thread (r, hf) runs the AVX accumulators 4hf..4hf+3 of lane quad member r -- positions
     // 32 st + 8 r + 4 hf + i -- with v_fma_mix (the f16 operands converted exactly, one
@@ -352,10 +274,6 @@ __device__ __forceinline__ void attn_d_run(const AttnDArgs & A, const int h, con
         for (; st + 4 <= ns; st += 4) { step(st); step(st + 1); step(st + 2); step(st + 3); }
         for (; st < ns; ++st) step(st);
         // S[l] = (r0 + r1) + (r2 + r3) over the quad, then t_i = S[i] + S[i + 4] (halves 0, 1)
-        auto qsum = [](float v) {
-            const float v0 = quad_bcast<0>(v), v1 = quad_bcast<1>(v), v2 = quad_bcast<2>(v), v3 = quad_bcast<3>(v);
-            return (v0 + v1) + (v2 + v3);
-        };
         // the other half's S (lane ^ 4 inside the 8-lane group): row_ror:n hands lane l the
         // value of lane (l - n) mod 16, so half 0 takes ror 12 (l + 4), half 1 ror 4 (l - 4)
         auto other = [&](float v) {
@@ -364,7 +282,7 @@ __device__ __forceinline__ void attn_d_run(const AttnDArgs & A, const int h, con
             const int b = __builtin_amdgcn_update_dpp(0, i, 0x12C, 0xF, 0xF, false);   // row_ror:12
             return __builtin_bit_cast(float, hf ? a : b);
         };
-        const float S0 = qsum(s0), S1 = qsum(s1), S2 = qsum(s2), S3 = qsum(s3);
+        const float S0 = quad_sum_bcast(s0), S1 = quad_sum_bcast(s1), S2 = quad_sum_bcast(s2), S3 = quad_sum_bcast(s3);
         const float t0 = S0 + other(S0), t1 = S1 + other(S1);
         const float t2 = S2 + other(S2), t3 = S3 + other(S3);
         o = (t0 + t1) + (t2 + t3);
@@ -399,46 +317,27 @@ __device__ __forceinline__ void attn_d_run(const AttnDArgs & A, const int h, con
         }
         o = (float) sumf;     // meaningful in the dim's first lane
     }
-#define LVK_OB_LANE ((tid & 7) == 0)
-#endif
     LVK_DT(10);
     float * ob = sc;          // reuse: 32 outputs (sc was last read before the barrier above)
-    if (LVK_OB_LANE) ob[q] = o;
-#undef LVK_OB_LANE
+    if ((tid & 7) == 0) ob[q] = o;
     bar();
     if (tid < 32) {
         const float v = ob[tid];
         if (A.out_f32) A.out_f32[d0 + tid] = v;
-        const int blk = d0 / 32;
         if constexpr (QT == Q4_0) {
-            float amax = fabsf(v);
-            for (int o2 = 16; o2 > 0; o2 >>= 1) { const float w = __shfl_xor(amax, o2); amax = w > amax ? w : amax; }
-            const float dd = amax / 7.0f;
-            const float id = (amax != 0.0f) ? 7.0f / amax : 0.0f;
-            const uint32_t qq = (uint32_t) ((int) __builtin_rintf(v * id) + 8) & 15u;
-            uint32_t part = qq << (4 * (tid & 7));
-            part |= __shfl_xor(part, 1);
-            part |= __shfl_xor(part, 2);
-            part |= __shfl_xor(part, 4);
-            const uint32_t w0 = __shfl(part, 0), w1 = __shfl(part, 8), w2 = __shfl(part, 16), w3 = __shfl(part, 24);
-            if (tid == 0) {
-                A.out.d[blk] = dd;
-                A.out.qs[blk] = make_uint4(w0, w1, w2, w3);
-            }
+            float dd;
+            uint4 qs;
+            mv::q40_block32(v, tid, dd, qs);
+            if (tid == 0) mv::actq_store_block(A.out, 0, d0 / 32, dd, qs);
         }
     }
     if constexpr (QT == Q4_1) {
         // quantize_row_q4_1 (ggml.c:847-920) of the 32 outputs staged in ob
         if (tid < 4) {
-            const int blk = d0 / 32;
             float dd, mm;
             uint32_t qw;
             mv::q41_block_lds(ob, tid, dd, mm, qw);
-            ((uint32_t *) (A.out.qs + blk))[tid] = qw;
-            if (tid == 0) {
-                A.out.d[blk] = dd;
-                A.out.m[blk] = mm;
-            }
+            mv::actq_store_block41(A.out, 0, d0 / 32, tid, dd, mm, qw);
         }
     }
     LVK_DT(11);
@@ -458,11 +357,10 @@ inline AttnDArgs attn_args(const AttnLaunch & A, void * gran, unsigned epoch) {
     a.sp = A.sp;
     a.E = A.n_embd;
     a.n_ctx = A.n_ctx;
-    a.scale = 1.0f / sqrtf((float) A.n_embd / (float) A.n_head);   // llama.cpp:1028
+    a.scale = attn_scale(A.n_embd, A.n_head);
     a.epoch = epoch;
     a.out = A.out;
     a.out_f32 = A.out_f32;
-    a.exp_mode = A.exp_computed;
     a.err = A.err;
     // short contexts skip the score exchange: every workgroup of a head scores all n_kv
     // positions itself (tools/probe r03: 4.8 vs 5.4 us at n_kv 33, 5.9 vs 6.3 at 101)
@@ -474,12 +372,6 @@ inline AttnDArgs attn_args(const AttnLaunch & A, void * gran, unsigned epoch) {
     a.short_max = short_max;
     a.seq_epochs = A.seq_epochs;
     return a;
-}
-
-template <int QT, int EM>
-__global__ __launch_bounds__(256) void k_attn_d(AttnDArgs A) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    attn_d_run<QT, EM, true>(A, blockIdx.x, blockIdx.y, smem, threadIdx.x);
 }
 
 }  // namespace
@@ -504,14 +396,10 @@ hipError_t launch_attention_decode(const AttnLaunch & A, void * gran, unsigned e
     const AttnDArgs a = attn_args(A, gran, epoch);
     const size_t lds = attn_lds(A.n_ctx);
     const dim3 grid(A.n_head, HD / 32);
-#define LVK_ATTN_EM(QT_)                                                                  \
-    switch (a.exp_mode) {                                                                 \
-        case 2: LVK_LAUNCH((k_attn_d<QT_, 2>), grid, dim3(256), lds, s, a); break;        \
-        case 1: LVK_LAUNCH((k_attn_d<QT_, 1>), grid, dim3(256), lds, s, a); break;        \
-        default: LVK_LAUNCH((k_attn_d<QT_, 0>), grid, dim3(256), lds, s, a); break;       \
-    }
-    if (A.out_qtype == Q4_1) { LVK_ATTN_EM(Q4_1) } else { LVK_ATTN_EM(Q4_0) }
-#undef LVK_ATTN_EM
+    with_exp_mode(A.exp_computed, [&](auto em) {
+        if (A.out_qtype == Q4_1) LVK_LAUNCH((k_attn_d<Q4_1, em()>), grid, dim3(256), lds, s, a);
+        else LVK_LAUNCH((k_attn_d<Q4_0, em()>), grid, dim3(256), lds, s, a);
+    });
     return hipGetLastError();
 }
 

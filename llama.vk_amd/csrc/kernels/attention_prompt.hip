@@ -1,8 +1,8 @@
 // attention_prompt.hip -- causal self-attention of a prompt batch (N > 1
 // tokens) over the f16 KV cache, bit-faithful to the reference graph
-// (llama.cpp:1010-1061) exactly like attention.hip, but organised for many
-// query tokens: the decode kernel's one-workgroup-per-(token, head) layout
-// re-streams K and V for every token (22 ms of a 512-token 7B prompt).
+// (llama.cpp:1010-1061), organised for many query tokens: the generic kernel's
+// (attention.hip) one-workgroup-per-(token, head) layout re-streams K and V for
+// every token (22 ms of a 512-token 7B prompt).
 //
 //   k_attn_p_scores  grid (H, ceil(N/16)/2): a pair of mirrored 16-token
 //                    blocks per workgroup (equal causal work everywhere); Q
@@ -19,7 +19,7 @@
 //                    Q4_0 block of the merged heads: quantize_row_q4_0
 //                    (ggml.c:621-685) fused, written as the Wo input (ActQ and,
 //                    for the MFMA Wo, the masked fragment image).
-#include "lvk_device.h"
+#include "attention_common.h"
 #include "mm41_common.h"
 #include "lvk_kernels.h"
 #include "matvec_common.h"
@@ -36,23 +36,7 @@ namespace lvk {
 
 namespace {
 
-constexpr int HD = 128;
-
-// the quad's 4 x 8 accumulators in the AVX2 F32Cx8_REDUCE order (lane j = AVX register j):
-// two DPP butterflies give (v0 + v1) + (v2 + v3) in every lane of the quad (fp
-// addition is commutative, so lane 1's v1 + v0 and lane 2's (v2 + v3) + (v0 + v1) are the same
-// bits) -- 4 instructions per accumulator instead of 7
-__device__ __forceinline__ float quad_reduce_bf(const float s[8]) {
-    float S[8];
-#pragma unroll
-    for (int l = 0; l < 8; ++l) {
-        const float x = s[l];
-        const float y = x + __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0xB1, 0xF, 0xF, false));
-        S[l] = y + __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, y), 0x4E, 0xF, 0xF, false));
-    }
-    const float t0 = S[0] + S[4], t1 = S[1] + S[5], t2 = S[2] + S[6], t3 = S[3] + S[7];
-    return (t0 + t1) + (t2 + t3);
-}
+constexpr int HD = ATTN_HD;
 
 // ---------------------------------------------------------------------------
 // scores + softmax.  A workgroup (4 waves) owns one head and two T-token blocks, the block
@@ -67,8 +51,7 @@ __device__ __forceinline__ float quad_reduce_bf(const float s[8]) {
 template <int T, int EM>
 __global__ __launch_bounds__(256) void k_attn_p_scores(const uint16_t * __restrict__ q16, const uint16_t * __restrict__ kc,
                                                        const uint16_t * __restrict__ exp_tab, const StepParams * sp,
-                                                       int E, int n_ctx, float scale, uint16_t * __restrict__ P,
-                                                       int exp_mode) {
+                                                       int E, int n_ctx, float scale, uint16_t * __restrict__ P) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int n_past = sp->n_past, N = sp->n_tokens;
     const int n_kv = n_past + N;
@@ -135,8 +118,7 @@ __global__ __launch_bounds__(256) void k_attn_p_scores(const uint16_t * __restri
                     const float a = acc[0][l] + acc[1][l], c = acc[2][l] + acc[3][l];
                     S[l] = a + c;
                 }
-                const float t0v = S[0] + S[4], t1v = S[1] + S[5], t2v = S[2] + S[6], t3v = S[3] + S[7];
-                float kq = (t0v + t1v) + (t2v + t3v);
+                float kq = f32cx8_hsum(S);
                 if (LVK_ATTN_P_KO & 1) kq = __builtin_bit_cast(float, (kr[0].x ^ (uint32_t) t) & 0xBFFFFFFFu) * 1e-30f;
                 if (live) sc[(size_t) t * n_ctx + p] = p <= n_past + t0 + t ? kq * scale : -INFINITY;
                 t += 4;
@@ -171,7 +153,7 @@ __global__ __launch_bounds__(256) void k_attn_p_scores(const uint16_t * __restri
             if (!(LVK_ATTN_P_KO & 4))
                 for (int p = lane; p <= lim; p += 64) {
                     const float e = (LVK_ATTN_P_KO & 2) ? row[p] - mx
-                                                        : f16_to_f32(exp_softmax<EM>(f32_to_f16(row[p] - mx), exp_tab, exp_mode));
+                                                        : f16_to_f32(exp_softmax<EM>(f32_to_f16(row[p] - mx), exp_tab));
                     sum += (double) e;
                     row[p] = e;
                 }
@@ -277,7 +259,7 @@ __global__ __launch_bounds__(256) void k_attn_p_pv(const uint16_t * __restrict__
     for (int a = 0; a < 4; ++a)
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
-            const float res = quad_reduce_bf(s[a][b]);
+            const float res = quad_reduce(s[a][b]);
             const int t = 4 * qt + b;
             const int lim = n_past + t0 + t;
             float v = res;
@@ -317,38 +299,19 @@ __global__ __launch_bounds__(256) void k_attn_p_pv(const uint16_t * __restrict__
                 float dd, mm;
                 uint32_t qword;
                 mv::q41_block_lds(ob + t * 33, e, dd, mm, qword);
-                const int base = (tid & 63) & ~3;
-                const uint32_t q0 = __shfl(qword, base), q1 = __shfl(qword, base + 1);
-                const uint32_t q2 = __shfl(qword, base + 2), q3 = __shfl(qword, base + 3);
-                if (e == 0) {
-                    out.d[(size_t) tok * out.nb + blk] = dd;
-                    out.m[(size_t) tok * out.nb + blk] = mm;
-                    out.qs[(size_t) tok * out.nb + blk] = make_uint4(q0, q1, q2, q3);
-                }
+                mv::actq_store_block41(out, tok, blk, e, dd, mm, qword);
                 if (xs41) act41_emit(tok, nb, blk, e, qword, dd, mm, (uint4 *) xm, xs41);
             }
             continue;
         }
-        float amax = fabsf(v);
-        for (int o2 = 16; o2 > 0; o2 >>= 1) { const float w = __shfl_xor(amax, o2); amax = w > amax ? w : amax; }
-        const float dd = amax / 7.0f;
-        const float id = (amax != 0.0f) ? 7.0f / amax : 0.0f;
-        const uint32_t qq = (uint32_t) ((int) __builtin_rintf(v * id) + 8) & 15u;
-        uint32_t part = qq << (4 * (e & 7));
-        part |= __shfl_xor(part, 1);
-        part |= __shfl_xor(part, 2);
-        part |= __shfl_xor(part, 4);
-        // the reference block (d + 16 nibble bytes): lanes e = 0, 8, 16, 24 hold its 4 words
-        const uint32_t w0 = __shfl(part, (tid & 32) + 0), w1 = __shfl(part, (tid & 32) + 8);
-        const uint32_t w2 = __shfl(part, (tid & 32) + 16), w3 = __shfl(part, (tid & 32) + 24);
-        if (e == 0) {
-            out.d[(size_t) tok * out.nb + blk] = dd;
-            out.qs[(size_t) tok * out.nb + blk] = make_uint4(w0, w1, w2, w3);
-        }
+        float dd;
+        uint4 qs;
+        mv::q40_block32(v, tid, dd, qs);
+        if (e == 0) mv::actq_store_block(out, tok, blk, dd, qs);
         if (xm && e < 4) {
             // the masked MFMA fragment image of the Wo input (mm_mfma.hip): group c = e holds
             // elements 8c..8c+7 = word c; chain 2c -> lane n, chain 2c+1 -> lane 48 + n
-            const uint32_t word = e == 0 ? w0 : e == 1 ? w1 : e == 2 ? w2 : w3;
+            const uint32_t word = e == 0 ? qs.x : e == 1 ? qs.y : e == 2 ? qs.z : qs.w;
             uint16_t hh[8];
 #pragma unroll
             for (int k = 0; k < 8; ++k)
@@ -373,22 +336,17 @@ hipError_t launch_attention_prompt(const AttnLaunch & A, uint16_t * p_scratch, c
     void * const xs41 = wo_image.xs;
     if (A.out_qtype == Q4_1 ? (xm != nullptr) != (xs41 != nullptr) || xda : A.out_qtype != Q4_0 || xs41 || (xm != nullptr) != (xda != nullptr))
         return hipErrorNotSupported;
-    const float scale = 1.0f / sqrtf((float) A.n_embd / (float) A.n_head);   // llama.cpp:1028
+    const float scale = attn_scale(A.n_embd, A.n_head);
     constexpr int T = 16;
     EventSplit ev;
     ev.first();
     const size_t lds1 = (size_t) T * 256 + (size_t) T * A.n_ctx * 4;
     const int nblk = (A.n_tokens + T - 1) / T;
     const dim3 g1(A.n_head, (nblk + 1) / 2);
-    if (A.exp_computed == 2)
-        LVK_LAUNCH((k_attn_p_scores<T, 2>), g1, dim3(256), lds1, s, A.q16, A.kc, A.exp_tab, A.sp, A.n_embd, A.n_ctx,
-                   scale, p_scratch, A.exp_computed);
-    else if (A.exp_computed == 1)
-        LVK_LAUNCH((k_attn_p_scores<T, 1>), g1, dim3(256), lds1, s, A.q16, A.kc, A.exp_tab, A.sp, A.n_embd, A.n_ctx,
-                   scale, p_scratch, A.exp_computed);
-    else
-        LVK_LAUNCH((k_attn_p_scores<T, 0>), g1, dim3(256), lds1, s, A.q16, A.kc, A.exp_tab, A.sp, A.n_embd, A.n_ctx,
-                   scale, p_scratch, A.exp_computed);
+    with_exp_mode(A.exp_computed, [&](auto em) {
+        LVK_LAUNCH((k_attn_p_scores<T, em()>), g1, dim3(256), lds1, s, A.q16, A.kc, A.exp_tab, A.sp, A.n_embd, A.n_ctx,
+                   scale, p_scratch);
+    });
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     const size_t lds2 = (size_t) 64 * A.n_ctx * 2;

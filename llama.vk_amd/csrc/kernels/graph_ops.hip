@@ -4,7 +4,7 @@
 // AVX2 build (each kernel cites the ggml.c function it follows).
 // These are operator-level kernels (one node per launch, generic strides): the fused
 // single-token and prompt paths of llama_eval are the matvec / MFMA / attention kernels.
-#include "lvk_device.h"
+#include "attention_common.h"
 #include "lvk_kernels.h"
 
 namespace lvk {
@@ -122,21 +122,16 @@ __global__ void k_g_rms_norm(GView s, GView d) {
 __global__ void k_g_soft_max(GView d, const uint16_t * exp_tab, int exp_mode) {
     const int64_t row = blockIdx.x;
     const int64_t i1 = row % d.ne[1], i2 = (row / d.ne[1]) % d.ne[2], i3 = row / (d.ne[1] * d.ne[2]);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     __shared__ float redf[4];
     __shared__ double redd[4];
+    auto bar = [] { __syncthreads(); };
     float mx = -INFINITY;
     for (int64_t i0 = tid; i0 < d.ne[0]; i0 += blockDim.x) {
         const float v = *(const float *) at(d, i0, i1, i2, i3);
         mx = v > mx ? v : mx;              // ggml_vec_max_f32: max = MAX(max, x)
     }
-    mx = wave_max_f(mx);
-    if (lane == 0) redf[wave] = mx;
-    __syncthreads();
-    {
-        const float a = redf[0] > redf[1] ? redf[0] : redf[1], b = redf[2] > redf[3] ? redf[2] : redf[3];
-        mx = a > b ? a : b;
-    }
+    mx = wg_max_f(mx, redf, bar);
     double sum = 0.0;
     for (int64_t i0 = tid; i0 < d.ne[0]; i0 += blockDim.x) {
         float * p = (float *) at(d, i0, i1, i2, i3);
@@ -146,10 +141,7 @@ __global__ void k_g_soft_max(GView d, const uint16_t * exp_tab, int exp_mode) {
         sum += (double) e;
         *p = e;
     }
-    sum = wave_sum_d(sum);
-    if (lane == 0) redd[wave] = sum;
-    __syncthreads();
-    sum = (redd[0] + redd[1]) + (redd[2] + redd[3]);
+    sum = wg_sum_d(sum, redd, bar);
     const float scl = (float) (1.0 / sum);
     for (int64_t i0 = tid; i0 < d.ne[0]; i0 += blockDim.x) {
         float * p = (float *) at(d, i0, i1, i2, i3);
@@ -245,8 +237,7 @@ __global__ void k_g_mm_dot(GView s0, const void * y, int64_t ne11, GView d) {
             const float a = sum[0][l] + sum[1][l], b = sum[2][l] + sum[3][l];
             S[l] = a + b;
         }
-        const float t0 = S[0] + S[4], t1 = S[1] + S[5], t2 = S[2] + S[6], t3 = S[3] + S[7];
-        const float res = (t0 + t1) + (t2 + t3);
+        const float res = f32cx8_hsum(S);
         float out;
         if (h) {
             double sumf = (double) res;

@@ -49,15 +49,14 @@ __device__ __forceinline__ uint16_t exp_f16(uint16_t hx, const uint16_t * __rest
     return tab[hx];
 }
 
-// softmax exp (exp_f16 semantics) for EM != 0 without a vector load on the common path:
+// softmax exp (exp_f16 semantics, EM = its mode compiled in) without a vector load on the
+// common path of EM != 0:
 // only NaN arguments (the table covers them; softmax arguments are <= 0 otherwise) take the
 // uploaded table, behind a wave-uniform branch, so no vmcnt wait -- which would also wait
 // for loads in flight (the decode attention's V DMA) -- sits in the loop
 template <int EM>
-__device__ __forceinline__ uint16_t exp_softmax(uint16_t hx, const uint16_t * __restrict__ tab, int mode) {
-    if constexpr (EM < 0) {
-        return exp_f16(hx, tab, mode);
-    } else if constexpr (EM == 0) {
+__device__ __forceinline__ uint16_t exp_softmax(uint16_t hx, const uint16_t * __restrict__ tab) {
+    if constexpr (EM == 0) {
         return tab[hx];
     } else {
         const float x = f16_to_f32(hx);

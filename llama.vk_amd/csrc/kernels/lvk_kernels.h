@@ -171,8 +171,8 @@ struct AttnLaunch {
     int seq_epochs = 0;       // decode attention: granule epoch = (sp->seq << 7) + epoch (no per-token zeroing)
 };
 hipError_t launch_attention(const AttnLaunch & A, hipStream_t s);
-// prompt batches (N > 1, Q4_0 / Q4_1 output): scores+softmax per (head, 32 tokens) then
-// P.V per (head, 32 tokens, 32 dims) with the Wo quantization fused
+// prompt batches (N > 1, Q4_0 / Q4_1 output): scores+softmax per (head, pair of mirrored
+// 16-token blocks) then P.V per (head, 32 tokens, 32 dims) with the Wo quantization fused
 // (attention_prompt.hip).  p_scratch: H*N*n_ctx f16; wo_image (optional, all of the type's
 // parts or none): also write the Wo input as the batched matmul's operand image.
 struct ActImage;

@@ -60,24 +60,36 @@ __device__ __forceinline__ uint32_t q40_pack8(const float v[8], float id) {
     return w;
 }
 
-// quantize 32 values held one per lane in a 32-lane half into a reference
-// Q4_0 block (quantize_row_q4_0 AVX2, ggml.c:621-685)
-__device__ __forceinline__ void quantize32_q40(float v, int lane, float * d_out, uint4 * qs_out, uint32_t * scratch) {
+// quantize_row_q4_0 (AVX2, ggml.c:621-685) of 32 values held one per lane of a 32-lane half
+// (element = lane & 31; call with the whole half active): every lane of the half returns the
+// block's d and its four nibble words
+__device__ __forceinline__ void q40_block32(float v, int lane, float & d, uint4 & qs) {
     float amax = fabsf(v);
     for (int o = 16; o > 0; o >>= 1) { const float w = __shfl_xor(amax, o); amax = w > amax ? w : amax; }
-    const float d = amax / 7.0f;
+    d = amax / 7.0f;
     const float id = (amax != 0.0f) ? 7.0f / amax : 0.0f;
     const uint32_t q = (uint32_t) ((int) __builtin_rintf(v * id) + 8) & 15u;
-    const int e = lane & 31;
-    uint32_t part = q << (4 * (e & 7));
+    uint32_t part = q << (4 * (lane & 7));
     part |= __shfl_xor(part, 1);
     part |= __shfl_xor(part, 2);
     part |= __shfl_xor(part, 4);
-    if ((e & 7) == 0) scratch[e >> 3] = part;
-    __builtin_amdgcn_wave_barrier();
-    if (e == 0) {
-        *d_out = d;
-        *qs_out = make_uint4(scratch[0], scratch[1], scratch[2], scratch[3]);
+    // lanes 0, 8, 16, 24 of the half hold the words
+    const int h0 = lane & 32;
+    qs = make_uint4(__shfl(part, h0), __shfl(part, h0 + 8), __shfl(part, h0 + 16), __shfl(part, h0 + 24));
+}
+
+// a finished block `blk` of token t's quantized activation row: one lane stores a Q4_0 block;
+// of a Q4_1 block lane k < 4 stores qs word k (q41_block_lds / q41_quad) and lane 0 d and m
+__device__ __forceinline__ void actq_store_block(const ActQ & out, int t, int blk, float d, uint4 qs) {
+    out.d[(size_t) t * out.nb + blk] = d;
+    out.qs[(size_t) t * out.nb + blk] = qs;
+}
+__device__ __forceinline__ void actq_store_block41(const ActQ & out, int t, int blk, int k, float d, float m,
+                                                   uint32_t qword) {
+    ((uint32_t *) (out.qs + (size_t) t * out.nb + blk))[k] = qword;
+    if (k == 0) {
+        out.d[(size_t) t * out.nb + blk] = d;
+        out.m[(size_t) t * out.nb + blk] = m;
     }
 }
 

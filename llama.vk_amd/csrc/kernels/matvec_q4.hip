@@ -298,7 +298,6 @@ __global__ __launch_bounds__(NT) void k_matvec_q40(Params P) {
         // 4-7 the matching w3 rows (llama.cpp:1085-1096)
         __syncthreads();
         float * ures = (float *) smem;                               // T x 64 floats
-        uint32_t * scratch = (uint32_t *) (smem + (size_t) T * 64 * 4);
 #pragma unroll
         for (int tt = 0; tt < T; ++tt)
             if (j == 0) ures[tt * 64 + wave * 8 + r] = res[tt];
@@ -309,9 +308,10 @@ __global__ __launch_bounds__(NT) void k_matvec_q40(Params P) {
             const float a1 = ures[tt * 64 + (e >> 2) * 8 + (e & 3)];        // w1 x
             const float a3 = ures[tt * 64 + (e >> 2) * 8 + 4 + (e & 3)];    // w3 x
             const float u = silu_mul(a1, a3, P.silu_tab);
-            const int t = t0 + tt;
-            quantize32_q40(u, lane, P.out_q.d + (size_t) t * P.out_q.nb + blk,
-                           P.out_q.qs + (size_t) t * P.out_q.nb + blk, scratch + (tid >> 5) * 4);
+            float d;
+            uint4 qs;
+            q40_block32(u, lane, d, qs);
+            if (e == 0) actq_store_block(P.out_q, t0 + tt, blk, d, qs);
         }
     }
 }
@@ -324,7 +324,7 @@ template <int NT, int T, int UMAX, int PRO, int EPI, int D, int KT>
 hipError_t go1(const Params & P, int ngroups, int ntok, hipStream_t s) {
     constexpr int NW = NT / 64;
     size_t lds = (size_t) T * P.nb * 32 + (size_t) T * P.NC * 128 + (size_t) NW * 2 * T * 1024 + T * NW * 8 + 64;
-    if (EPI == EPI_SWIGLU) lds = std::max(lds, (size_t) T * 256 + NT / 2 * 16);
+    if (EPI == EPI_SWIGLU) lds = std::max(lds, (size_t) T * 256);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     dim3 grid(ngroups / NW, (ntok + T - 1) / T);
     LVK_LAUNCH((k_matvec_q40<NT, T, UMAX, PRO, EPI, D, KT>), grid, dim3(NT), lds, s, P);

@@ -265,7 +265,7 @@ static int attention_impl(const uint16_t * kc, const uint16_t * vc, const float 
         LVK_HIP(hipMemcpy(out, od, (size_t) n * n_embd * 4, hipMemcpyDeviceToHost));
         if (scores_out) {
             LVK_HIP(hipMemcpy(scores_out, A.scores, (size_t) n * n_head * n_ctx * 4, hipMemcpyDeviceToHost));
-            // debug: the f16 probabilities overwrite the second half of scores_out's bytes? no -- appended
+            // the f16 probabilities follow the scores (lvk_ops.h: scores_out holds 1.5x the floats)
             LVK_HIP(hipMemcpy(scores_out + (size_t) n * n_head * n_ctx, pd, (size_t) n * n_head * n_ctx * 2,
                               hipMemcpyDeviceToHost));
         }
