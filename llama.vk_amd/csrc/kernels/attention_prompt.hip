@@ -20,9 +20,7 @@
 //                    (ggml.c:621-685) fused, written as the Wo input (ActQ and,
 //                    for the MFMA Wo, the masked fragment image).
 #include "attention_common.h"
-#include "mm41_common.h"
-#include "lvk_kernels.h"
-#include "matvec_common.h"
+#include "mm_common.h"
 
 #include <cstdlib>
 
@@ -309,14 +307,10 @@ __global__ __launch_bounds__(256) void k_attn_p_pv(const uint16_t * __restrict__
         mv::q40_block32(v, tid, dd, qs);
         if (e == 0) mv::actq_store_block(out, tok, blk, dd, qs);
         if (xm && e < 4) {
-            // the masked MFMA fragment image of the Wo input (mm_mfma.hip): group c = e holds
-            // elements 8c..8c+7 = word c; chain 2c -> lane n, chain 2c+1 -> lane 48 + n
+            // the masked MFMA fragment image of the Wo input (mm_common.h act40_emit): group
+            // c = e holds elements 8c..8c+7 = word c
             const uint32_t word = e == 0 ? qs.x : e == 1 ? qs.y : e == 2 ? qs.z : qs.w;
-            uint16_t hh[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k)
-                hh[k] = __builtin_bit_cast(uint16_t, (_Float16) (float) ((int) ((word >> (4 * k)) & 15u) - 8));
-            act40_emit(tok, nb, blk, e, hh, dd, xm, xda);
+            act40_emit(tok, nb, blk, e, word, dd, xm, xda);
         }
     }
 }

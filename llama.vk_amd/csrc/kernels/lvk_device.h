@@ -252,49 +252,6 @@ __device__ __forceinline__ float warp_max(float v) {
     return v;
 }
 
-// Masked B fragment image of the MFMA prompt matmul (mm_mfma.hip): token t, block b of nb,
-// chain pair c (chains 2c, 2c+1), fragment lane l.  The fragments of chain pairs 2q and 2q+1
-// sit side by side per lane, so a wave fetches two MFMA B operands with one 16-byte-per-lane
-// load (the texture unit's cost is per load instruction: 8-byte loads moved half the bytes
-// per cycle).  Returns the index in 8-byte units.
-__device__ __forceinline__ size_t xm_slot(int t, int nb, int b, int c, int l) {
-    return ((((size_t) (t >> 4) * nb + b) * 2 + (c >> 1)) * 64 + l) * 2 + (c & 1);
-}
-
-// The Q4_0 operand writes of group c (elements 8c .. 8c+7) of block b of token t, h[e] the
-// f16 bits of q_e - 8: chain 2c -> fragment lane n = t % 16 (h = jj = 0), chain 2c+1 -> lane
-// 48 + n (h = jj = 1), each in the order e0 e2 e1 e3; the lane of group 0 also stores the
-// block scale d (the Q4_1 counterpart: mm41_common.h act41_emit)
-__device__ __forceinline__ void act40_emit(int t, int nb, int b, int c, const uint16_t (&h)[8], float d,
-                                           uint2 * __restrict__ xm, float * __restrict__ da) {
-    xm[xm_slot(t, nb, b, c, t & 15)] = make_uint2(h[0] | (uint32_t) h[2] << 16, h[1] | (uint32_t) h[3] << 16);
-    xm[xm_slot(t, nb, b, c, 48 + (t & 15))] = make_uint2(h[4] | (uint32_t) h[6] << 16, h[5] | (uint32_t) h[7] << 16);
-    if (c == 0) da[(size_t) t * nb + b] = d;
-}
-
-// token of workgroup i in a one-workgroup-per-token launch of ceil(N/128)*128 workgroups:
-// workgroup i runs on XCD i % 8, and the 16 tokens of token tile tau all go to XCD tau % 8,
-// so the 16-byte pieces they write into the same fragment-image lines (xm_slot) meet in one
-// L2 instead of being merged from 8 XCDs (>= N: no token)
-__device__ __forceinline__ int xcd_grouped_token(int i) {
-    const int tau = ((i >> 7) << 3) | (i & 7);
-    return tau * 16 + ((i >> 3) & 15);
-}
-
-// prompt-matmul tile of workgroup slot L (its XCD-contiguous index, mm_mfma.hip): row tile
-// rt, token tile tt.  Super tiles of R = 4 row tiles x every token tile with the token tiles
-// outer, so the 64 workgroups an XCD runs at once share 4 weight tiles and 16 activation
-// tiles in its L2 instead of 2 weight tiles and the whole activation image (7B 512-token
-// prompt 45.3 -> 43.7 ms, profiles/r04_prompt_variants.jsonl); the row tiles left over after
-// the last whole super tile go row tile outer, token tile inner
-__device__ __forceinline__ void mm_tile(int L, int ntt, int nrt, int & rt, int & tt) {
-    constexpr int R = 4;
-    tt = L % ntt;
-    rt = L / ntt;
-    const int per = R * ntt, sidx = L / per, wi = L % per;
-    if (R * sidx + R - 1 < nrt) { tt = wi / R; rt = R * sidx + wi % R; }
-}
-
 // fmaf(f16 half HA of a, f16 half HB of b, c): v_fma_mix converts both f16 operands
 // exactly and rounds once, the same result as fmaf on the converted values
 template <int HA, int HB>

@@ -213,17 +213,17 @@ inline const uint4 * q41_wsum(const QMatrix & w) {
 
 // ---------------------------------------------------------------------------
 // Batched (N > 1) matmul, bit-exact like launch_matvec.  One interface for the three
-// weight types; launch_mm dispatches on w.qtype:
+// weight types; launch_mm (mm_launch.hip) dispatches on w.qtype:
 //   Q4_0 (mm_mfma.hip): the matrix cores produce the per-chain integer partials, the VALU
 //     runs the reference fp32 chains.  Weights: the octet image, or QMatrix::a16 when built.
 //   Q4_1 (mm_mfma41.hip): the matrix cores also produce the cross-term sums and the scale
 //     products.  Weights: QMatrix::a16 + QMatrix::side, both from launch_build_mm41.
 //   F16 (mm_f16.hip): the fp32 chains of matvec_f16.hip, tiled over tokens.
 // The activations reach the kernels as an operand image of the weight type:
-//   xm : Q4_0 / Q4_1 the masked MFMA B-fragment image (lvk_device.h xm_slot);
+//   xm : Q4_0 / Q4_1 the masked MFMA B-fragment image (mm_common.h xm_slot);
 //        F16 the paired-step f16 rows, N rounded up to MM_F16_TPAD rows
 //   da : Q4_0 the block scales [N][K/32]
-//   xs : Q4_1 the side image [N/16][K/32][64] x 16 B (mm41_common.h act41_emit)
+//   xs : Q4_1 the side image [N/16][K/32][64] x 16 B (mm_common.h act41_emit)
 // xm must be ZEROED once at allocation: the writers only ever store the active fragment
 // slots (Q4), and the padding rows' products are computed and dropped (F16).
 struct ActImage {
@@ -268,7 +268,7 @@ struct MmLaunch {
     ActImage out;
 };
 // which epilogues a type's kernels implement; launch_mm returns hipErrorNotSupported for the others
-inline bool mm_epi_supported(int qtype, int epi) {
+constexpr bool mm_epi_supported(int qtype, int epi) {
     switch (epi) {
         case EPI_STORE: case EPI_RESID: case EPI_SWIGLU_F32: return qtype == F16 || qtype == Q4_0 || qtype == Q4_1;
         case EPI_ROPE_KV: return qtype == Q4_0 || qtype == Q4_1;
@@ -279,7 +279,8 @@ inline bool mm_epi_supported(int qtype, int epi) {
 // the matrix's shape and images fit its type's kernels
 bool mm_supported(const QMatrix & w);
 hipError_t launch_mm(const MmLaunch & L, int epi, hipStream_t s);
-// the per-type halves of launch_act / launch_actq_to_image / launch_mm (reached through them)
+// the per-type halves of launch_act / launch_actq_to_image / launch_mm (reached through them,
+// which check the arguments: these only fill their parameter block and launch)
 hipError_t act_q40(const float * x, const float * g, int N, int K, const ActImage & out, hipStream_t s);
 hipError_t act_q41(const float * x, const float * g, int N, int K, const ActImage & out, hipStream_t s);
 hipError_t act_f16(const float * x, const float * g, int N, int K, const ActImage & out, hipStream_t s);

@@ -60,14 +60,36 @@ __device__ __forceinline__ uint32_t q40_pack8(const float v[8], float id) {
     return w;
 }
 
+// the Q4_0 block scale d of a block's amax; returns the quantization factor id
+__device__ __forceinline__ float q40_scale(float amax, float & d) {
+    d = amax / 7.0f;                                          // ggml.c:651
+    return (amax != 0.0f) ? 7.0f / amax : 0.0f;               // ggml.c:653
+}
+
+// quantize_row_q4_0 (AVX2, ggml.c:621-685) of one block held by a lane quad (lane k: elements
+// 8k..8k+7): every lane returns d, lane k the reference nibble word of its elements
+__device__ __forceinline__ void q40_quad(const float (&v)[8], float & d, uint32_t & qword) {
+    float amax = 0.0f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const float a = fabsf(v[e]);
+        amax = a > amax ? a : amax;
+    }
+    // block amax (ggml.c:636-649)
+    const float o0 = quad_bcast<0>(amax), o1 = quad_bcast<1>(amax);
+    const float o2 = quad_bcast<2>(amax), o3 = quad_bcast<3>(amax);
+    const float m01 = o1 > o0 ? o1 : o0, m23 = o3 > o2 ? o3 : o2;
+    amax = m23 > m01 ? m23 : m01;
+    qword = q40_pack8(v, q40_scale(amax, d));
+}
+
 // quantize_row_q4_0 (AVX2, ggml.c:621-685) of 32 values held one per lane of a 32-lane half
 // (element = lane & 31; call with the whole half active): every lane of the half returns the
 // block's d and its four nibble words
 __device__ __forceinline__ void q40_block32(float v, int lane, float & d, uint4 & qs) {
     float amax = fabsf(v);
     for (int o = 16; o > 0; o >>= 1) { const float w = __shfl_xor(amax, o); amax = w > amax ? w : amax; }
-    d = amax / 7.0f;
-    const float id = (amax != 0.0f) ? 7.0f / amax : 0.0f;
+    const float id = q40_scale(amax, d);
     const uint32_t q = (uint32_t) ((int) __builtin_rintf(v * id) + 8) & 15u;
     uint32_t part = q << (4 * (lane & 7));
     part |= __shfl_xor(part, 1);
@@ -334,7 +356,9 @@ __device__ __forceinline__ void pro_norm_unit(float (&v)[8], const float4 & ga, 
 }
 
 // quantize_row_q4_0 of the block a lane quad holds, unit un = this lane's 8 elements, into the
-// table (act_store; the quad's first lane also writes d)
+// table (act_store; the quad's first lane also writes d).  q40_quad's arithmetic written out:
+// through the call hipcc schedules the decode kernels' prologues differently
+// (profiles/mm_pieces_kernel_resources.md), and those kernels are tuned as they stand
 __device__ __forceinline__ void q40_unit_store(const float (&v)[8], int un, bool live, uint32_t * act, float * dxp) {
     float amax = 0.0f;
 #pragma unroll
@@ -523,93 +547,5 @@ __device__ __forceinline__ void mv_epilogue_rows(const MvArgs & P, const float (
 }
 
 }  // namespace mv
-// the RoPE + KV epilogue of a prompt-matmul lane (mm_mfma.hip, mm_mfma41.hip): the lane holds
-// rows m0 + 32w + 8q + 4h + p (p = 0..3) of token n; rows [0, E) Q, [E, 2E) K, [2E, 3E) V.
-// rope_kv_cs loads the 8 cos / sin pairs (before the reduction and any store: issued between
-// stores they each wait a full latency), rope_kv_store does RoPE (ggml.c:7209-7232, as
-// k_rope_kv) and the f16 stores of the cache views (llama.cpp:1010-1024)
-__device__ __forceinline__ void rope_kv_cs(const RopeKV & r, int N, int n, int h, int w, int m0, float2 (&cs)[4][2]) {
-    const int pos = r.sp->n_past + (n < N ? n : N - 1);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int e = (m0 + 32 * w + 8 * q + 4 * h) % r.hd;
-#pragma unroll
-        for (int pp = 0; pp < 2; ++pp) cs[q][pp] = r.rope[(size_t) pos * (r.hd / 2) + (e >> 1) + pp];
-    }
-}
-__device__ __forceinline__ void rope_kv_store(const RopeKV & r, const float (&res)[16], const float2 (&cs)[4][2], int n,
-                                              int h, int w, int m0) {
-    const int pos = r.sp->n_past + n;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int row = m0 + 32 * w + 8 * q + 4 * h;
-        const int which = row / r.E, e = row - which * r.E;
-        if (which < 2) {
-            uint32_t hw[2];
-#pragma unroll
-            for (int pp = 0; pp < 4; pp += 2) {
-                const float x0 = res[4 * q + pp], x1 = res[4 * q + pp + 1];
-                const float2 c = cs[q][pp >> 1];
-                const float a0 = x0 * c.x, b0 = x1 * c.y;
-                const float o0 = a0 - b0;
-                const float a1 = x0 * c.y, b1 = x1 * c.x;
-                const float o1 = a1 + b1;
-                hw[pp >> 1] = (uint32_t) f32_to_f16(o0) | (uint32_t) f32_to_f16(o1) << 16;
-            }
-            uint16_t * dst = which == 0 ? r.q16 + (size_t) n * r.E + e : r.kc + (size_t) pos * r.E + e;
-            *(uint2 *) dst = make_uint2(hw[0], hw[1]);
-        } else {
-#pragma unroll
-            for (int pp = 0; pp < 4; ++pp) r.vc[(size_t) (e + pp) * r.n_ctx + pos] = f32_to_f16(res[4 * q + pp]);
-        }
-    }
-}
-
-// The stores of a prompt-matmul lane's 16 results res (mm_mfma.hip, mm_mfma41.hip; rows and
-// lanes as above, the jj = 0 lanes hold the results): EPI_STORE, EPI_RESID (y += res),
-// EPI_SWIGLU_F32 and EPI_ROPE_KV (cs from rope_kv_cs)
-template <int EPI>
-__device__ __forceinline__ void mm_epi_store(const float (&res)[16], float * y, int ldy, const uint16_t * silu_tab,
-                                             const RopeKV & rk, const float2 (&cs)[4][2], int N, int n, int lane, int w,
-                                             int m0) {
-    const int h = lane >> 5;
-    const int jj = (lane >> 4) & 1;
-    if constexpr (EPI == EPI_SWIGLU_F32) {
-        // W1|W3 image interleaved per 4 rows: h = 0 lanes hold the w1 rows, h = 1 the w3 rows of the
-        // same outputs (llama.cpp:1085-1096)
-        float o[16];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) o[i] = __shfl_xor(res[i], 32);
-        if (jj == 0 && h == 0 && n < N) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                float uu[4];
-#pragma unroll
-                for (int p = 0; p < 4; ++p) {
-                    const float sl = f16_to_f32(silu_tab[f32_to_f16(res[4 * q + p])]);  // ggml.c:2495
-                    uu[p] = sl * o[4 * q + p];                                          // ggml_mul
-                }
-                const int row = m0 + 32 * w + 8 * q;
-                *(float4 *) (y + (size_t) n * ldy + row / 2) = make_float4(uu[0], uu[1], uu[2], uu[3]);
-            }
-        }
-    } else if constexpr (EPI == EPI_ROPE_KV) {
-        // RoPE + the f16 q / K / V stores (rope_kv_store); a wave's 32 rows lie in one of Q, K, V
-        if (jj == 0 && n < N) rope_kv_store(rk, res, cs, n, h, w, m0);
-    } else {
-        if (jj == 0 && n < N) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                float4 * yp = (float4 *) (y + (size_t) n * ldy + m0 + 32 * w + 8 * q + 4 * h);
-                if constexpr (EPI == EPI_RESID) {
-                    const float4 r = *yp;                 // the residual add, as mv_epilogue
-                    *yp = make_float4(res[4 * q] + r.x, res[4 * q + 1] + r.y, res[4 * q + 2] + r.z, res[4 * q + 3] + r.w);
-                } else {
-                    *yp = make_float4(res[4 * q], res[4 * q + 1], res[4 * q + 2], res[4 * q + 3]);
-                }
-            }
-        }
-    }
-}
 
 }  // namespace lvk

@@ -10,6 +10,7 @@
 // the f16 operands was chosen over v_pk_fma_f32 on pre-converted operands: it needs no
 // conversion instructions and half the activation bytes, and both are exact here.
 #include "f16_common.h"
+#include "mm_common.h"
 
 namespace lvk {
 
@@ -113,12 +114,7 @@ hipError_t mm_f16(const MmLaunch & L, int epi, hipStream_t s) {
     MmParams P{};
     P.img = w.nib; P.M = w.M; P.K = w.K; P.G = (w.M + 7) / 8;
     P.x16 = (const uint4 *) L.x.xm; P.N = L.N; P.y = L.y; P.ldy = L.ldy; P.silu_tab = L.silu_tab;
-    switch (epi) {
-        case EPI_STORE: return go_t<EPI_STORE>(P, s);
-        case EPI_RESID: return go_t<EPI_RESID>(P, s);
-        case EPI_SWIGLU_F32: return go_t<EPI_SWIGLU_F32>(P, s);
-    }
-    return hipErrorNotSupported;
+    return mm_epi_dispatch<F16>(epi, [&](auto e) { return go_t<decltype(e)::value>(P, s); });
 }
 
 }  // namespace lvk

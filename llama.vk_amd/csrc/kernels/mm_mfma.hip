@@ -27,7 +27,7 @@
 //     in the chain order e0 e2 e1 e3.
 //   B (activations): Q4_0-quantized tokens as f16 values q-8, written by the
 //     activation quantizer straight into the masked fragment image
-//       xm[token tile][block][c/2][64 lanes][c%2] x 8 B   (lvk_device.h xm_slot)
+//       xm[token tile][block][c/2][64 lanes][c%2] x 8 B   (mm_common.h xm_slot)
 //     (lane (h, jj, n): chain 2c+h of token n when h == jj, else zero).  The
 //     token tile's fragments of one sub-chunk (8 blocks x 2 x 64 lanes x 16 B)
 //     are staged once per workgroup in LDS, double-buffered, and every wave
@@ -36,27 +36,17 @@
 //     barrier per chunk); s = dw*da of 32 rows x 16 tokens x 2 blocks comes
 //     from one v_mfma_f32_32x32x1f32 outer product (exact f32 products).
 // Workgroup = 4 waves, tile 128 rows x 16 tokens (wave w: rows 32w..32w+31,
-// all 8 chains: 64 accumulator registers); workgroups are mapped so the 8
-// XCDs each sweep contiguous row tiles with the token tiles innermost (the
-// weight tile is fetched into that XCD's L2 once for all its token tiles).
-#include "lvk_device.h"
-#include "lvk_kernels.h"
-#include "matvec_common.h"
-
-#include <cstdlib>
+// all 8 chains: 64 accumulator registers), in the XCD-aware tile order (mm_common.h
+// mm_origin).  This file: the kernel, its activation quantizers and its f16 weight image
+// builder; the tile, the operand layouts and the epilogue it shares with the Q4_1 kernel
+// are in mm_common.h, the interface dispatch in mm_launch.hip.
+#include "mm_common.h"
 
 namespace lvk {
 
 namespace {
 
-typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
-typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
-typedef float f32x32_t __attribute__((ext_vector_type(32)));
-
-constexpr int TM = 128;     // rows per workgroup
-constexpr int TN = 16;      // tokens per workgroup (one token tile)
-constexpr int NT = 256;     // threads (4 waves)
+constexpr int TM = MM_TM, TN = MM_TN, NT = MM_NT;   // the tile (mm_common.h)
 constexpr int PDA = 4;      // A16 variant: A blocks in flight per wave
 
 constexpr int DWS = TM + 8;                         // padded row stride of the dw image (conflict-free stores)
@@ -73,15 +63,10 @@ struct MmParams {
     const uint4 * nib;
     const float4 * scl;
     const uint2 * a16;       // A16 variant: f16 A-fragment image [M/32][nb][4][64] (QMatrix::a16)
-    int M, K, nb, NC;
+    int M, nb, NC;
     const uint2 * xm;        // masked B fragment image [ntt][nb][4][64]
     const float * da;        // [N][nb]
-    int N;                   // tokens
-    int ntt;                 // token tiles
-    float * y;               // output
-    int ldy;
-    const uint16_t * silu_tab;
-    RopeKV rk;               // EPI_ROPE_KV only
+    MmOut o;                 // tokens N, token tiles ntt, the output y, ...
     uint2 * xq;              // EPI_SWIGLU_Q: the W2 input's fragment image, scales, blocks per token
     float * xqda;
     int nbq;
@@ -108,70 +93,39 @@ __device__ __forceinline__ half4_t unpack_chain(uint32_t X, uint32_t sel) {
     return r;
 }
 
-// AVX2 horizontal order (ggml.c:2019-2024) and the epilogue of a wave's 32 rows x 16 tokens:
-// lane (h, n, jj) register set c holds chain 2c+jj; r_j = a_j + a_{j+4} (same lane, sets c and
-// c+2), (r0+r2) | (r1+r3) in lanes jj = 0 | 1, then across the lane pair (xor 16)
-template <int EPI>
-__device__ __forceinline__ void mm_store(const MmParams & P, const f32x16_t (&acc)[4], int lane, int w, int m0, int n0) {
-    const int h = lane >> 5;
-    const int jj = (lane >> 4) & 1;
-    float2 cs[4][2];                                  // EPI_ROPE_KV: cos / sin (rope_kv_cs)
-    if constexpr (EPI == EPI_ROPE_KV) rope_kv_cs(P.rk, P.N, n0 + (lane & 15), h, w, m0, cs);
+// EPI_SWIGLU_Q, the end of the W1|W3 matmul: SwiGLU as EPI_SWIGLU_F32, then quantize_row_q4_0
+// of the W2 input (ggml.c:621-685) straight into its fragment image.  The wave's 16 outputs
+// (features m0/2 + 16w ..) are half of Q4_0 block b -- groups 2 (w & 1) and 2 (w & 1) + 1 --
+// the other half in wave w ^ 1, the amax exchanged through LDS (free after the main loop's
+// last barrier)
+__device__ __forceinline__ void swiglu_q_store(const MmParams & P, const f32x16_t (&acc)[4], int lane, int w, int m0,
+                                               int n0) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem_e[];
+    const int n = n0 + (lane & 15);
+    const bool first = (lane >> 4) == 0;              // h = jj = 0: the w1 rows' results
     float res[16];
+    mm_hsum(acc, res);
+    float uu[16];
+    float am = 0.0f;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-        const float r0 = acc[0][i] + acc[2][i];       // r_jj     = a_jj + a_{jj+4}
-        const float r2 = acc[1][i] + acc[3][i];       // r_{2+jj} = a_{2+jj} + a_{6+jj}
-        const float v = r0 + r2;
-        res[i] = v + __shfl_xor(v, 16);               // (r0 + r2) + (r1 + r3) in the jj = 0 lanes
+        uu[i] = mv::silu_mul(res[i], __shfl_xor(res[i], 32), P.o.silu_tab);
+        const float a = fabsf(uu[i]);
+        am = a > am ? a : am;
     }
-
-    // ---- epilogue: jj = 0 lanes hold rows 32w + 8q + 4h + p (i = 4q + p) of token n ----
-    const int n = n0 + (lane & 15);
-    if constexpr (EPI == EPI_SWIGLU_Q) {
-        // SwiGLU as EPI_SWIGLU_F32, then quantize_row_q4_0 of the W2 input (ggml.c:621-685, the
-        // arithmetic of k_act_q40_f16_tile) straight into its fragment image: the wave's 16
-        // outputs (features m0/2 + 16w ..) are half of Q4_0 block b, the other half in wave
-        // w ^ 1, the amax exchanged through LDS (free after the main loop's last barrier)
-        extern __shared__ __attribute__((aligned(16))) uint8_t smem_e[];
-        float uu[16];
-        float am = 0.0f;
+    __syncthreads();
+    float * red = (float *) smem_e;
+    if (first) red[w * 16 + (lane & 15)] = am;
+    __syncthreads();
+    if (first && n < P.o.N) {
+        const float ao = red[(w ^ 1) * 16 + (lane & 15)];
+        const float amax = (w & 1) ? (am > ao ? am : ao) : (ao > am ? ao : am);
+        float d;
+        const float id = mv::q40_scale(amax, d);
+        const int b = ((m0 >> 1) + 16 * w) >> 5;
 #pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const float o = __shfl_xor(res[i], 32);
-            const float sl = f16_to_f32(P.silu_tab[f32_to_f16(res[i])]);    // ggml.c:2495
-            uu[i] = sl * o;                                                  // llama.cpp:1096
-            const float a = fabsf(uu[i]);
-            am = a > am ? a : am;
-        }
-        __syncthreads();
-        float * red = (float *) smem_e;
-        if (jj == 0 && h == 0) red[w * 16 + (lane & 15)] = am;
-        __syncthreads();
-        if (jj == 0 && h == 0 && n < P.N) {
-            const float ao = red[(w ^ 1) * 16 + (lane & 15)];
-            const float amax = (w & 1) ? (am > ao ? am : ao) : (ao > am ? ao : am);
-            const float d = amax / 7.0f;                              // ggml.c:651
-            const float id = (amax != 0.0f) ? 7.0f / amax : 0.0f;     // ggml.c:653
-            const int b = ((m0 >> 1) + 16 * w) >> 5;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                uint32_t hh[4];
-#pragma unroll
-                for (int p = 0; p < 4; ++p) {
-                    const int qv = ((int) __builtin_rintf(uu[4 * q + p] * id) + 8) & 15;   // ggml.c:655-684
-                    hh[p] = __builtin_bit_cast(uint16_t, (_Float16) (float) (qv - 8));
-                }
-                // elements 16 (w & 1) + 4q + p of the block: group c = 2 (w & 1) + q / 2, its
-                // first half (q even) in lane n, its second in lane 48 + n (k_act_q40_f16 order)
-                const int c = 2 * (w & 1) + (q >> 1);
-                P.xq[xm_slot(n, P.nbq, b, c, (q & 1) ? 48 + (n & 15) : (n & 15))] =
-                    make_uint2(hh[0] | hh[2] << 16, hh[1] | hh[3] << 16);
-            }
-            if ((w & 1) == 0) P.xqda[(size_t) n * P.nbq + b] = d;
-        }
-    } else {
-        mm_epi_store<EPI>(res, P.y, P.ldy, P.silu_tab, P.rk, cs, P.N, n, lane, w, m0);
+        for (int g = 0; g < 2; ++g)
+            act40_emit(n, P.nbq, b, 2 * (w & 1) + g, mv::q40_pack8(uu + 8 * g, id), d, P.xq, P.xqda);
     }
 }
 
@@ -184,16 +138,8 @@ __global__ __launch_bounds__(NT, 2) void k_mm_q40_mfma(MmParams P) {
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int w = tid >> 6;
-    // XCD-aware tile order: workgroup b runs on XCD b % 8; give each XCD a
-    // contiguous range of (row tile, token tile) with token tiles innermost
-    const int nwg = gridDim.x;
-    const int bid = blockIdx.x;
-    const int full = nwg & ~7;
-    const int L = bid < full ? (bid & 7) * (full >> 3) + (bid >> 3) : bid;
-    int tt, rt;
-    mm_tile(L, P.ntt, P.M / TM, rt, tt);
-    const int m0 = rt * TM;
-    const int n0 = tt * TN;
+    const MmOrigin og = mm_origin(P.o.ntt, P.M / TM);
+    const int rt = og.rt, tt = og.tt, m0 = og.m0, n0 = og.n0;
     const int nb = P.nb, NC = P.NC;
     const int G0 = m0 / 8;
     const int U = nb / 8;                      // sub-chunks of 8 blocks
@@ -211,7 +157,7 @@ __global__ __launch_bounds__(NT, 2) void k_mm_q40_mfma(MmParams P) {
         for (int i = 0; i < 2; ++i) {
             const int Li = i * NT + tid;
             const int n = Li >> 5, jb = Li & 31;
-            const int tok = min(n0 + n, P.N - 1);
+            const int tok = min(n0 + n, P.o.N - 1);
             rda[i] = P.da[(size_t) tok * nb + min(c * 32 + jb, nb - 1)];
         }
     };
@@ -277,10 +223,7 @@ __global__ __launch_bounds__(NT, 2) void k_mm_q40_mfma(MmParams P) {
     };
 
     f32x16_t acc[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[c][i] = 0.0f;
+    mm_zero(acc);
 
     uint32_t X[4][4];                                     // signed octet nibbles -> unsigned q
     auto make_x = [&](const uint4 (&A)[4]) {
@@ -367,65 +310,24 @@ __global__ __launch_bounds__(NT, 2) void k_mm_q40_mfma(MmParams P) {
                                           // chunk ch-1 / sub-chunk u-1 free again
     }
 
-    mm_store<EPI>(P, acc, lane, w, m0, n0);
+    if constexpr (EPI == EPI_SWIGLU_Q) swiglu_q_store(P, acc, lane, w, m0, n0);
+    else mm_finish<EPI>(P.o, acc, lane, w, m0, n0);
 }
 
 // ---------------------------------------------------------------------------
-// Activation quantizer for the MFMA path: x[t] (optionally rms_norm * g) ->
-// quantize_row_q4_0 (AVX2 branch, ggml.c:621-685) -> f16 values q-8 in the
-// A-unpack k order + da.  One workgroup per token; the RMSNorm double sum is
-// the same per-thread strided / wave tree / in-order-waves reduction as the
-// matvec prologue (matvec_q4.hip prologue_norm).
+// Activation quantizer for the MFMA path: x[t] (optionally rms_norm * g, mm_common.h
+// act_units) -> quantize_row_q4_0 (AVX2 branch, ggml.c:621-685; mv::q40_quad) -> the
+// fragment image + da (act40_emit).  One workgroup per token, one lane quad per block.
 // ---------------------------------------------------------------------------
 template <bool NORM>
 __global__ __launch_bounds__(256) void k_act_q40_f16(const float * __restrict__ x, const float * __restrict__ g,
                                                      int N, int K, uint2 * __restrict__ xm, float * __restrict__ da) {
-    const int t = xcd_grouped_token(blockIdx.x);
-    if (t >= N) return;
-    const int tid = threadIdx.x;
-    const int nunits = K / 8;
-    const float * xr = x + (size_t) t * K;
-    float scale = 1.0f;
-    if constexpr (NORM) scale = rms_scale_256(xr, K);
-    for (int u0 = 0; u0 < nunits; u0 += 256) {
-        const int u = u0 + tid;
-        const bool live = u < nunits;          // nunits % 4 == 0: quads are all live or all dead
-        float v[8];
-        if (live) {
-            const float4 a = *(const float4 *) (xr + u * 8), b = *(const float4 *) (xr + u * 8 + 4);
-            v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-            if constexpr (NORM) {
-                const float4 ga = *(const float4 *) (g + u * 8), gb = *(const float4 *) (g + u * 8 + 4);
-                const float gg[8] = {ga.x, ga.y, ga.z, ga.w, gb.x, gb.y, gb.z, gb.w};
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float yn = v[e] * scale;     // ggml_vec_scale_f32 (ggml.c:6076)
-                    v[e] = gg[e] * yn;                 // ggml_mul(repeat(g), cur) (llama.cpp:984)
-                }
-            }
-        } else {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = 0.0f;
-        }
-        float amax = 0.0f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { const float a = fabsf(v[e]); amax = a > amax ? a : amax; }
-        const float o0 = quad_bcast<0>(amax), o1 = quad_bcast<1>(amax);
-        const float o2 = quad_bcast<2>(amax), o3 = quad_bcast<3>(amax);
-        const float m01 = o1 > o0 ? o1 : o0, m23 = o3 > o2 ? o3 : o2;
-        amax = m23 > m01 ? m23 : m01;
-        const float d = amax / 7.0f;                              // ggml.c:651
-        const float id = (amax != 0.0f) ? 7.0f / amax : 0.0f;     // ggml.c:653
-        if (live) {
-            uint16_t h[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const int q = ((int) __builtin_rintf(v[e] * id) + 8) & 15;   // ggml.c:655-684
-                h[e] = __builtin_bit_cast(uint16_t, (_Float16) (float) (q - 8));
-            }
-            act40_emit(t, K / 32, u >> 2, u & 3, h, d, xm, da);
-        }
-    }
+    act_units<NORM>(x, g, N, K, [&](int t, int u, bool live, const float (&v)[8]) {
+        float d;
+        uint32_t qword;
+        mv::q40_quad(v, d, qword);
+        if (live) act40_emit(t, K / 32, u >> 2, u & 3, qword, d, xm, da);
+    });
 }
 
 // The quantizer without RMSNorm (the W2 input) by token tiles: a wave takes one 32-block b of
@@ -444,31 +346,16 @@ __global__ __launch_bounds__(256) void k_act_q40_f16_tile(const float * __restri
     const bool live = t < N;
     float v[8];
     if (live) {
-        const float * xp = x + (size_t) t * K + b * 32 + c * 8;
-        const float4 a = *(const float4 *) xp, bb = *(const float4 *) (xp + 4);
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = bb.x; v[5] = bb.y; v[6] = bb.z; v[7] = bb.w;
+        const float4 * xp = (const float4 *) (x + (size_t) t * K + b * 32 + c * 8);
+        mv::unit_vals(xp[0], xp[1], v);
     } else {
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = 0.0f;
     }
-    float amax = 0.0f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { const float a = fabsf(v[e]); amax = a > amax ? a : amax; }
-    const float o0 = quad_bcast<0>(amax), o1 = quad_bcast<1>(amax);
-    const float o2 = quad_bcast<2>(amax), o3 = quad_bcast<3>(amax);
-    const float m01 = o1 > o0 ? o1 : o0, m23 = o3 > o2 ? o3 : o2;
-    amax = m23 > m01 ? m23 : m01;
-    const float d = amax / 7.0f;                              // ggml.c:651
-    const float id = (amax != 0.0f) ? 7.0f / amax : 0.0f;     // ggml.c:653
-    if (live) {
-        uint16_t h[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const int q = ((int) __builtin_rintf(v[e] * id) + 8) & 15;   // ggml.c:655-684
-            h[e] = __builtin_bit_cast(uint16_t, (_Float16) (float) (q - 8));
-        }
-        act40_emit(t, nb, b, c, h, d, xm, da);
-    }
+    float d;
+    uint32_t qword;
+    mv::q40_quad(v, d, qword);
+    if (live) act40_emit(t, nb, b, c, qword, d, xm, da);
 }
 
 // pre-quantized Q4_0 blocks (ActQ: d + reference nibble qs) -> masked fragment image + da
@@ -479,72 +366,25 @@ __global__ void k_actq_to_f16(ActQ q, int N, int K, uint2 * __restrict__ xm, flo
     const int c = (int) (idx & 3);
     const long tb = idx >> 2;
     const uint4 qs = q.qs[tb];
-    const uint32_t wd[4] = {qs.x, qs.y, qs.z, qs.w};
-    const uint32_t word = wd[c];               // elements 8c..8c+7: element 2k = byte k low nibble
-    uint16_t h[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const int qv = (int) ((word >> (4 * e)) & 15u);
-        h[e] = __builtin_bit_cast(uint16_t, (_Float16) (float) (qv - 8));
-    }
+    const uint32_t wd[4] = {qs.x, qs.y, qs.z, qs.w};     // word c = elements 8c..8c+7: element 2k = byte k low nibble
     const int t = (int) (tb / nb), b = (int) (tb % nb);
-    act40_emit(t, nb, b, c, h, c == 0 ? q.d[tb] : 0.0f, xm, da);
+    act40_emit(t, nb, b, c, wd[c], c == 0 ? q.d[tb] : 0.0f, xm, da);
 }
 
-// RoPE mode 0 (ggml.c:7156-7227) + KV append (llama.cpp:996-1008) of the
-// stored Q|K|V rows [N][3E] -> q16 [N][E], K cache [pos][E], V cache [E][pos]
-__global__ void k_rope_kv(const float * __restrict__ qkv, int N, int E, int hd, const float2 * __restrict__ rope,
-                          const StepParams * __restrict__ sp, int n_ctx, uint16_t * __restrict__ q16,
-                          uint16_t * __restrict__ kc, uint16_t * __restrict__ vc, int kv32) {
-    const int t = blockIdx.y;
-    const int e2 = blockIdx.x * blockDim.x + threadIdx.x;     // pair index over Q|K (E/2 each) then V
-    const int pos = sp->n_past + t;
-    const float * row = qkv + (size_t) t * 3 * E;
-    if (e2 < E) {                // Q and K pairs: e2 in [0, E): which = e2 / (E/2)
-        const int which = e2 / (E / 2);
-        const int e = 2 * (e2 - which * (E / 2));
-        const float x0 = row[which * E + e], x1 = row[which * E + e + 1];
-        const int i0 = e % hd;
-        const float2 cs = rope[(size_t) pos * (hd / 2) + (i0 >> 1)];
-        const float a0 = x0 * cs.x, b0 = x1 * cs.y;
-        const float o0 = a0 - b0;
-        const float a1 = x0 * cs.y, b1 = x1 * cs.x;
-        const float o1 = a1 + b1;
-        if (which == 0) {
-            kv_store(q16, (size_t) t * E + e, o0, kv32);
-            kv_store(q16, (size_t) t * E + e + 1, o1, kv32);
-        } else {
-            kv_store(kc, (size_t) pos * E + e, o0, kv32);
-            kv_store(kc, (size_t) pos * E + e + 1, o1, kv32);
-        }
-    } else if (e2 < E + E / 2) {
-        const int e = 2 * (e2 - E);
-        kv_store(vc, (size_t) e * n_ctx + pos, row[2 * E + e], kv32);
-        kv_store(vc, (size_t) (e + 1) * n_ctx + pos, row[2 * E + e + 1], kv32);
-    }
-}
-
-// f16 A-fragment image of a Q4_0 octet image (QMatrix::a16): a16[M/32][nb][c/2][lane][c%2] x 8 B,
-// lane (rho, h) = row 32 rt + rho, chain 2c + h: its 4 elements as f16 (q - 8) in the
-// fragment order e0 e2 e1 e3 (the order the activation image uses).  One thread per
-// 8-byte fragment, read from the octet word that holds the chain (k_repack_q40 layout).
-__global__ void k_a16_from_octet(const uint4 * __restrict__ nib, int M, int K, uint2 * __restrict__ a16) {
+// f16 A-fragment image of a Q4_0 octet image (QMatrix::a16, mm_common.h a16_slot): lane
+// (rho, h) = row 32 rt + rho, chain 2c + h: its 4 elements as f16 (q - 8) in the fragment
+// order e0 e2 e1 e3 (the order the activation image uses).  One thread per 8-byte fragment.
+__global__ void k_a16_from_octet(const uint4 * __restrict__ nibi, int M, int K, uint2 * __restrict__ a16) {
     const int nb = K / 32, NC = (nb + 31) / 32;
     const long idx = (long) blockIdx.x * blockDim.x + threadIdx.x;     // ((rt * nb + b) * 4 + c) * 64 + lane
     if (idx >= (long) (M / 32) * nb * 256) return;
     const int lane = (int) (idx & 63), c = (int) ((idx >> 6) & 3);
     const long rb = idx >> 8;
     const int b = (int) (rb % nb), rt = (int) (rb / nb);
-    const int row = rt * 32 + (lane & 31), jc = 2 * c + (lane >> 5);
-    const uint4 v = nib[(((size_t) (row >> 3) * NC + (b >> 5)) * 4 + ((b & 31) >> 3)) * 64 + 8 * (row & 7) + jc];
-    const uint32_t wd[4] = {v.x, v.y, v.z, v.w};
-    const uint32_t t = ((wd[(b & 7) >> 1] >> (16 * (b & 1))) & 0xFFFFu) ^ 0x8888u;   // byte0: e0 e1, byte1: e2 e3
-    uint16_t hq[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) hq[e] = __builtin_bit_cast(uint16_t, (_Float16) (float) ((int) ((t >> (4 * e)) & 15u) - 8));
-    // chain pairs 2q, 2q+1 side by side per lane (as xm_slot): one 16-byte load per 2 MFMAs
-    a16[((((size_t) rt * nb + b) * 2 + (c >> 1)) * 64 + lane) * 2 + (c & 1)] =
-        make_uint2(hq[0] | (uint32_t) hq[2] << 16, hq[1] | (uint32_t) hq[3] << 16);
+    // the octet image holds signed nibbles: ^ 8 gives q.  byte0: e0 e1, byte1: e2 e3
+    const uint32_t t = octet_chain_field(nibi, rt * 32 + (lane & 31), b, NC, 2 * c + (lane >> 5)) ^ 0x8888u;
+    a16[a16_slot(rt, nb, b, c, lane)] = make_uint2(h16m8(nib(t, 0)) | h16m8(nib(t, 2)) << 16,
+                                                   h16m8(nib(t, 1)) | h16m8(nib(t, 3)) << 16);
 }
 
 }  // namespace
@@ -558,47 +398,24 @@ hipError_t launch_build_a16(const QMatrix & w, void * a16, hipStream_t s) {
     return hipGetLastError();
 }
 
-bool mm_supported(const QMatrix & w) {
-    switch (w.qtype) {
-        case Q4_0: return w.M % TM == 0 && w.K % 256 == 0;
-        case Q4_1: return w.a16 && w.side && w.M % TM == 0 && w.K % 256 == 0;
-        case F16: return w.M >= 1 && w.K % 256 == 0;
-    }
-    return false;
-}
-
 hipError_t mm_q40(const MmLaunch & L, int epi, hipStream_t s) {
     const QMatrix & w = L.w;
     MmParams P{};
-    if (epi == EPI_ROPE_KV) {
-        if (w.M != 3 * L.rk->E || L.rk->E % 32 || L.rk->hd % 4 || !L.rk->sp) return hipErrorInvalidValue;
-        P.rk = *L.rk;
-    }
     if (epi == EPI_SWIGLU_Q) {
         if (w.M % 64 || !L.silu_tab || !L.out.xm || !L.out.da) return hipErrorInvalidValue;
         P.xq = (uint2 *) L.out.xm; P.xqda = L.out.da; P.nbq = w.M / 64;
     }
-    P.nib = w.nib; P.scl = (const float4 *) w.scl;
-    P.M = w.M; P.K = w.K; P.nb = w.K / 32; P.NC = (P.nb + 31) / 32;
-    P.xm = (const uint2 *) L.x.xm; P.da = L.x.da; P.N = L.N; P.ntt = (L.N + TN - 1) / TN;
-    P.y = L.y; P.ldy = L.ldy; P.silu_tab = L.silu_tab;
-    P.a16 = (const uint2 *) w.a16;
-    const dim3 grid((w.M / TM) * P.ntt);
-#define LVK_MM_GO(E)                                                                      \
-    do {                                                                                  \
-        if (P.a16) LVK_LAUNCH((k_mm_q40_mfma<E, true>), grid, dim3(NT), LDS_TOTAL, s, P); \
-        else LVK_LAUNCH((k_mm_q40_mfma<E, false>), grid, dim3(NT), LDS_TOTAL, s, P);      \
-    } while (0)
-    switch (epi) {
-        case EPI_STORE: LVK_MM_GO(EPI_STORE); break;
-        case EPI_RESID: LVK_MM_GO(EPI_RESID); break;
-        case EPI_SWIGLU_F32: LVK_MM_GO(EPI_SWIGLU_F32); break;
-        case EPI_ROPE_KV: LVK_MM_GO(EPI_ROPE_KV); break;
-        case EPI_SWIGLU_Q: LVK_MM_GO(EPI_SWIGLU_Q); break;
-        default: return hipErrorNotSupported;
-    }
-#undef LVK_MM_GO
-    return hipGetLastError();
+    P.nib = w.nib; P.scl = (const float4 *) w.scl; P.a16 = (const uint2 *) w.a16;
+    P.M = w.M; P.nb = w.K / 32; P.NC = (P.nb + 31) / 32;
+    P.xm = (const uint2 *) L.x.xm; P.da = L.x.da;
+    P.o = mm_out(L, epi);
+    const dim3 grid((w.M / TM) * P.o.ntt);
+    return mm_epi_dispatch<Q4_0>(epi, [&](auto e) {
+        constexpr int E = decltype(e)::value;
+        if (P.a16) LVK_LAUNCH((k_mm_q40_mfma<E, true>), grid, dim3(NT), LDS_TOTAL, s, P);
+        else LVK_LAUNCH((k_mm_q40_mfma<E, false>), grid, dim3(NT), LDS_TOTAL, s, P);
+        return hipGetLastError();
+    });
 }
 
 hipError_t act_q40(const float * x, const float * g, int N, int K, const ActImage & out, hipStream_t s) {
@@ -616,46 +433,7 @@ hipError_t actq_image_q40(const ActQ & q, int N, int K, const ActImage & out, hi
     return hipGetLastError();
 }
 
-// ---- the type dispatch of the batched matmul interface (lvk_kernels.h) ----
-static bool image_complete(int qtype, const ActImage & im) {
-    return im.xm && (qtype != Q4_0 || im.da) && (qtype != Q4_1 || im.xs);
-}
-
-hipError_t launch_act(int qtype, const float * x, const float * g, int N, int K, const ActImage & out, hipStream_t s) {
-    if (K % 256 || N <= 0 || !x || !image_complete(qtype, out)) return hipErrorInvalidValue;
-    switch (qtype) {
-        case Q4_0: return act_q40(x, g, N, K, out, s);
-        case Q4_1: return act_q41(x, g, N, K, out, s);
-        case F16: return act_f16(x, g, N, K, out, s);
-    }
-    return hipErrorNotSupported;
-}
-
-hipError_t launch_actq_to_image(int qtype, const ActQ & q, int N, int K, const ActImage & out, hipStream_t s) {
-    if (qtype != Q4_0 && qtype != Q4_1) return hipErrorNotSupported;
-    if (K % 32 || N <= 0 || !image_complete(qtype, out)) return hipErrorInvalidValue;
-    return qtype == Q4_0 ? actq_image_q40(q, N, K, out, s) : actq_image_q41(q, N, K, out, s);
-}
-
-hipError_t launch_mm(const MmLaunch & L, int epi, hipStream_t s) {
-    if (!mm_epi_supported(L.w.qtype, epi)) return hipErrorNotSupported;
-    if (!mm_supported(L.w) || L.N <= 0 || !image_complete(L.w.qtype, L.x) || (epi == EPI_ROPE_KV) != (L.rk != nullptr))
-        return hipErrorInvalidValue;
-    switch (L.w.qtype) {
-        case Q4_0: return mm_q40(L, epi, s);
-        case Q4_1: return mm_q41(L, epi, s);
-        default: return mm_f16(L, epi, s);
-    }
-}
-
-hipError_t launch_rope_kv(const float * qkv, int N, int E, int hd, const float2 * rope, const StepParams * sp,
-                          int n_ctx, uint16_t * q16, uint16_t * kc, uint16_t * vc, hipStream_t s, int kv32) {
-    const int pairs = E + E / 2;
-    LVK_LAUNCH(k_rope_kv, dim3((pairs + 255) / 256, N), dim3(256), 0, s, qkv, N, E, hd, rope, sp, n_ctx, q16, kc, vc,
-               kv32);
-    return hipGetLastError();
-}
-
 }  // namespace lvk
 
+// this translation unit's rms_scale_256 counters (k_act_q40_f16<true>), probe build only
 LVK_RMS_ACCESSOR(lvk_probe_rms_mm)

@@ -28,27 +28,20 @@
 // Operand images (all built so a lane's operand is one 16-byte load):
 //   weights a16  [M/32][nb][2][64] x 16 B  chain fragments (as the Q4_0 image, values q)
 //           side [M/32][nb][64] x 16 B     {S operand (4 x f16), d | m (f32), 0}
-//   tokens  xm   [N/16][nb][2][64] x 16 B  masked chain fragments (lvk_device.h xm_slot)
+//   tokens  xm   [N/16][nb][2][64] x 16 B  masked chain fragments (mm_common.h xm_slot)
 //           xs   [N/16][nb][64] x 16 B     {S operand, d | m, (m | d) masked}
 // No LDS and no barrier: every operand streams straight into registers, 3 blocks deep
 // (13B 512-token prompt: 1 block 188.7 ms, 2: 172.4, 3: 170.0, 4: 235.8 -- spills).
-// Workgroup = 4 waves, tile 128 rows x 16 tokens, XCD-aware tile order (mm_mfma.hip).
-#include "lvk_device.h"
-#include "lvk_kernels.h"
-#include "matvec_common.h"
-#include "mm41_common.h"
+// Workgroup = 4 waves, tile 128 rows x 16 tokens, XCD-aware tile order (mm_common.h mm_origin).
+// Two kernels stream the operands differently (a register ring, an LDS-DMA ring) and share
+// the block arithmetic (block41) and, with the Q4_0 kernel, the tile and the epilogue.
+#include "mm_common.h"
 
 namespace lvk {
 
 namespace {
 
-typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
-typedef float f32x32_t __attribute__((ext_vector_type(32)));
-
-constexpr int TM = 128;     // rows per workgroup
-constexpr int TN = 16;      // tokens per workgroup
-constexpr int NT = 256;     // 4 waves
+constexpr int TM = MM_TM, NT = MM_NT;   // the tile (mm_common.h)
 constexpr int PD = 3;       // blocks of every operand in flight per wave
 
 struct Mm41Params {
@@ -56,36 +49,44 @@ struct Mm41Params {
     const uint4 * side;      // [M/32][nb][64]
     const uint4 * xm;        // [ntt][nb][2][64]
     const uint4 * xs;        // [ntt][nb][64]
-    int M, nb, N, ntt;
-    float * y;
-    int ldy;
-    const uint16_t * silu_tab;
-    RopeKV rk;               // EPI_ROPE_KV only
+    int M, nb;
+    MmOut o;                 // tokens N, token tiles ntt, the output y, ...
 };
 
 struct Blk {                 // one block's operands of one lane
     uint4 a[2], b[2], sa, sb;
 };
 
-// AVX2 horizontal order + offset, then the role's store (shared by both kernels)
-template <int EPI>
-__device__ __forceinline__ void epilogue41(const Mm41Params & P, const f32x16_t (&acc)[4], const f32x16_t & off,
-                                           int lane, int w, int m0, int n0) {
-    // AVX2 horizontal order (ggml.c:2250-2256) as in mm_mfma.hip, then + off * 32 (QK)
-    const int h = lane >> 5;
-    float2 cs[4][2];                                  // EPI_ROPE_KV: cos / sin (rope_kv_cs)
-    if constexpr (EPI == EPI_ROPE_KV) rope_kv_cs(P.rk, P.N, n0 + (lane & 15), h, w, m0, cs);
-    float res[16];
+// One block of a lane's chains (both kernels): the scale products, the chain partials P and
+// cross-term operands S from the matrix cores, then the reference's fmaf chains and offset
+__device__ __forceinline__ void block41(const Blk & o, f32x16_t (&acc)[4], f32x16_t & off) {
+    const float sw = __builtin_bit_cast(float, o.sa.z);      // d | m of the row
+    const float sb1 = __builtin_bit_cast(float, o.sb.z);     // d | m of the token
+    const float sb2 = __builtin_bit_cast(float, o.sb.w);     // (m | d) where h == jj, else 0
+    // dx*dy (registers 0..15) and mx*my (16..31); dx*my | mx*dy by column parity
+    const f32x32_t SM = __builtin_amdgcn_mfma_f32_32x32x1f32(sw, sb1, (f32x32_t){}, 0, 0, 0);
+    const f32x16_t SX = __builtin_amdgcn_mfma_f32_32x32x2f32(sw, sb2, (f32x16_t){}, 0, 0, 0);
+    const half4_t ax = __builtin_bit_cast(half4_t, make_uint2(o.sa.x, o.sa.y));
+    const uint32_t bfr[8] = {o.b[0].x, o.b[0].y, o.b[0].z, o.b[0].w, o.b[1].x, o.b[1].y, o.b[1].z, o.b[1].w};
+    const uint32_t afr[8] = {o.a[0].x, o.a[0].y, o.a[0].z, o.a[0].w, o.a[1].x, o.a[1].y, o.a[1].z, o.a[1].w};
 #pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const float r0 = acc[0][i] + acc[2][i];
-        const float r2 = acc[1][i] + acc[3][i];
-        const float v = r0 + r2;
-        const float hs = v + __shfl_xor(v, 16);
-        res[i] = hs + off[i] * 32.0f;
+    for (int c = 0; c < 4; ++c) {
+        const half4_t a = __builtin_bit_cast(half4_t, make_uint2(afr[2 * c], afr[2 * c + 1]));
+        const half4_t b = __builtin_bit_cast(half4_t, make_uint2(bfr[2 * c], bfr[2 * c + 1]));
+        // the S operand's B fragment: slot c of the token's sums (or of e_c)
+        const uint32_t yw = (c < 2) ? o.sb.x : o.sb.y;
+        const uint32_t ym = yw & ((c & 1) ? 0xFFFF0000u : 0x0000FFFFu);
+        const half4_t bs = __builtin_bit_cast(half4_t, (c < 2) ? make_uint2(ym, 0u) : make_uint2(0u, ym));
+        const f32x16_t Pc = __builtin_amdgcn_mfma_f32_32x32x8f16(a, b, (f32x16_t){}, 0, 0, 0);
+        const f32x16_t Sc = __builtin_amdgcn_mfma_f32_32x32x8f16(ax, bs, (f32x16_t){}, 0, 0, 0);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            acc[c][i] = __builtin_fmaf(SM[i], Pc[i], acc[c][i]);      // ggml.c:2244
+            acc[c][i] = __builtin_fmaf(SX[i], Sc[i], acc[c][i]);      // ggml.c:2247
+        }
     }
-    const int n = n0 + (lane & 15);
-    mm_epi_store<EPI>(res, P.y, P.ldy, P.silu_tab, P.rk, cs, P.N, n, lane, w, m0);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) off[i] = off[i] + SM[16 + i];      // ggml.c:2226
 }
 
 template <int EPI>
@@ -93,14 +94,8 @@ __global__ __launch_bounds__(NT, 2) void k_mm_q41_mfma(Mm41Params P) {
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int w = tid >> 6;
-    const int nwg = gridDim.x;
-    const int bid = blockIdx.x;
-    const int full = nwg & ~7;
-    const int L = bid < full ? (bid & 7) * (full >> 3) + (bid >> 3) : bid;
-    int tt, rtile;
-    mm_tile(L, P.ntt, P.M / TM, rtile, tt);
-    const int m0 = rtile * TM;
-    const int n0 = tt * TN;
+    const MmOrigin og = mm_origin(P.o.ntt, P.M / TM);
+    const int tt = og.tt, m0 = og.m0, n0 = og.n0;
     const int nb = P.nb;
     const int rt = m0 / 32 + w;                              // this wave's 32-row tile
 
@@ -118,12 +113,8 @@ __global__ __launch_bounds__(NT, 2) void k_mm_q41_mfma(Mm41Params P) {
     };
 
     f32x16_t acc[4], off;
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[c][i] = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) off[i] = 0.0f;
+    mm_zero(acc);
+    mm_zero(off);
 
     Blk ring[PD];
 #pragma unroll
@@ -135,33 +126,7 @@ __global__ __launch_bounds__(NT, 2) void k_mm_q41_mfma(Mm41Params P) {
             const int blk = b0 + d;
             if (blk >= nb) break;
             Blk & o = ring[d];
-            const float sw = __builtin_bit_cast(float, o.sa.z);      // d | m of the row
-            const float sb1 = __builtin_bit_cast(float, o.sb.z);     // d | m of the token
-            const float sb2 = __builtin_bit_cast(float, o.sb.w);     // (m | d) where h == jj, else 0
-            // dx*dy (registers 0..15) and mx*my (16..31); dx*my | mx*dy by column parity
-            const f32x32_t SM = __builtin_amdgcn_mfma_f32_32x32x1f32(sw, sb1, (f32x32_t){}, 0, 0, 0);
-            const f32x16_t SX = __builtin_amdgcn_mfma_f32_32x32x2f32(sw, sb2, (f32x16_t){}, 0, 0, 0);
-            const half4_t ax = __builtin_bit_cast(half4_t, make_uint2(o.sa.x, o.sa.y));
-            const uint32_t bfr[8] = {o.b[0].x, o.b[0].y, o.b[0].z, o.b[0].w, o.b[1].x, o.b[1].y, o.b[1].z, o.b[1].w};
-            const uint32_t afr[8] = {o.a[0].x, o.a[0].y, o.a[0].z, o.a[0].w, o.a[1].x, o.a[1].y, o.a[1].z, o.a[1].w};
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const half4_t a = __builtin_bit_cast(half4_t, make_uint2(afr[2 * c], afr[2 * c + 1]));
-                const half4_t b = __builtin_bit_cast(half4_t, make_uint2(bfr[2 * c], bfr[2 * c + 1]));
-                // the S operand's B fragment: slot c of the token's sums (or of e_c)
-                const uint32_t yw = (c < 2) ? o.sb.x : o.sb.y;
-                const uint32_t ym = yw & ((c & 1) ? 0xFFFF0000u : 0x0000FFFFu);
-                const half4_t bs = __builtin_bit_cast(half4_t, (c < 2) ? make_uint2(ym, 0u) : make_uint2(0u, ym));
-                const f32x16_t Pc = __builtin_amdgcn_mfma_f32_32x32x8f16(a, b, (f32x16_t){}, 0, 0, 0);
-                const f32x16_t Sc = __builtin_amdgcn_mfma_f32_32x32x8f16(ax, bs, (f32x16_t){}, 0, 0, 0);
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    acc[c][i] = __builtin_fmaf(SM[i], Pc[i], acc[c][i]);      // ggml.c:2244
-                    acc[c][i] = __builtin_fmaf(SX[i], Sc[i], acc[c][i]);      // ggml.c:2247
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < 16; ++i) off[i] = off[i] + SM[16 + i];      // ggml.c:2226
+            block41(o, acc, off);
             // refill this slot PD blocks ahead (its MFMAs have consumed it)
             load(min(blk + PD, nb - 1), o);
 #pragma unroll
@@ -169,7 +134,7 @@ __global__ __launch_bounds__(NT, 2) void k_mm_q41_mfma(Mm41Params P) {
         }
     }
 
-    epilogue41<EPI>(P, acc, off, lane, w, m0, n0);
+    mm_finish<EPI>(P.o, acc, lane, w, m0, n0, off);
 }
 
 // ---------------------------------------------------------------------------
@@ -202,14 +167,8 @@ __global__ __launch_bounds__(NT, OCC41) void k_mm_q41_dma(Mm41Params P) {
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int w = tid >> 6;
-    const int nwg = gridDim.x;
-    const int bid = blockIdx.x;
-    const int full = nwg & ~7;
-    const int L = bid < full ? (bid & 7) * (full >> 3) + (bid >> 3) : bid;
-    int tt, rtile;
-    mm_tile(L, P.ntt, P.M / TM, rtile, tt);
-    const int m0 = rtile * TM;
-    const int n0 = tt * TN;
+    const MmOrigin og = mm_origin(P.o.ntt, P.M / TM);
+    const int tt = og.tt, m0 = og.m0, n0 = og.n0;
     const int nb = P.nb;
     const int rt = m0 / 32 + w;
 
@@ -230,12 +189,8 @@ __global__ __launch_bounds__(NT, OCC41) void k_mm_q41_dma(Mm41Params P) {
     };
 
     f32x16_t acc[4], off;
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[c][i] = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) off[i] = 0.0f;
+    mm_zero(acc);
+    mm_zero(off);
 
 #pragma unroll
     for (int sl = 0; sl < RS; ++sl) issue(min(sl, nb - 1), sl);
@@ -253,83 +208,27 @@ __global__ __launch_bounds__(NT, OCC41) void k_mm_q41_dma(Mm41Params P) {
         issue(min(blk + RS, nb - 1), slot);
         slot = slot + 1 == RS ? 0 : slot + 1;
 
-        const float sw = __builtin_bit_cast(float, o.sa.z);
-        const float sb1 = __builtin_bit_cast(float, o.sb.z);
-        const float sb2 = __builtin_bit_cast(float, o.sb.w);
-        const f32x32_t SM = __builtin_amdgcn_mfma_f32_32x32x1f32(sw, sb1, (f32x32_t){}, 0, 0, 0);
-        const f32x16_t SX = __builtin_amdgcn_mfma_f32_32x32x2f32(sw, sb2, (f32x16_t){}, 0, 0, 0);
-        const half4_t ax = __builtin_bit_cast(half4_t, make_uint2(o.sa.x, o.sa.y));
-        const uint32_t bfr[8] = {o.b[0].x, o.b[0].y, o.b[0].z, o.b[0].w, o.b[1].x, o.b[1].y, o.b[1].z, o.b[1].w};
-        const uint32_t afr[8] = {o.a[0].x, o.a[0].y, o.a[0].z, o.a[0].w, o.a[1].x, o.a[1].y, o.a[1].z, o.a[1].w};
-        auto mfma_p = [&](int c) __attribute__((always_inline)) {
-            const half4_t a = __builtin_bit_cast(half4_t, make_uint2(afr[2 * c], afr[2 * c + 1]));
-            const half4_t b = __builtin_bit_cast(half4_t, make_uint2(bfr[2 * c], bfr[2 * c + 1]));
-            return __builtin_amdgcn_mfma_f32_32x32x8f16(a, b, (f32x16_t){}, 0, 0, 0);
-        };
-        auto mfma_s = [&](int c) __attribute__((always_inline)) {
-            const uint32_t yw = (c < 2) ? o.sb.x : o.sb.y;
-            const uint32_t ym = yw & ((c & 1) ? 0xFFFF0000u : 0x0000FFFFu);
-            const half4_t bs = __builtin_bit_cast(half4_t, (c < 2) ? make_uint2(ym, 0u) : make_uint2(0u, ym));
-            return __builtin_amdgcn_mfma_f32_32x32x8f16(ax, bs, (f32x16_t){}, 0, 0, 0);
-        };
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const f32x16_t Pc = mfma_p(c);
-            const f32x16_t Sc = mfma_s(c);
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                acc[c][i] = __builtin_fmaf(SM[i], Pc[i], acc[c][i]);      // ggml.c:2244
-                acc[c][i] = __builtin_fmaf(SX[i], Sc[i], acc[c][i]);      // ggml.c:2247
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 16; ++i) off[i] = off[i] + SM[16 + i];      // ggml.c:2226
+        block41(o, acc, off);
 #pragma unroll
         for (int c = 0; c < 4; ++c) asm volatile("" : "+v"(acc[c]));
     }
     // the trailing refills must land before the workgroup's LDS is released
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    epilogue41<EPI>(P, acc, off, lane, w, m0, n0);
+    mm_finish<EPI>(P.o, acc, lane, w, m0, n0, off);
 }
 
-// activation quantizer for the Q4_1 MFMA path: x[t] (optionally rms_norm * g) ->
-// quantize_row_q4_1 (AVX2 branch, ggml.c:847-920; matvec_common.h q41_quad) -> the
-// fragment and side images.  One workgroup per token, one lane quad per block.
+// activation quantizer for the Q4_1 MFMA path: x[t] (optionally rms_norm * g, mm_common.h
+// act_units) -> quantize_row_q4_1 (AVX2 branch, ggml.c:847-920; mv::q41_quad) -> the
+// fragment and side images (act41_emit).  One workgroup per token, one lane quad per block.
 template <bool NORM>
 __global__ __launch_bounds__(256) void k_act_q41_f16(const float * __restrict__ x, const float * __restrict__ g, int N,
                                                      int K, uint4 * __restrict__ xm, uint4 * __restrict__ xs) {
-    const int t = xcd_grouped_token(blockIdx.x);
-    if (t >= N) return;
-    const int tid = threadIdx.x;
-    const int nunits = K / 8;
-    const float * xr = x + (size_t) t * K;
-    float scale = 1.0f;
-    if constexpr (NORM) scale = rms_scale_256(xr, K);
-    for (int u0 = 0; u0 < nunits; u0 += 256) {
-        const int u = u0 + tid;
-        const bool live = u < nunits;          // nunits % 4 == 0: quads are all live or all dead
-        float v[8];
-        if (live) {
-            const float4 a = *(const float4 *) (xr + u * 8), b = *(const float4 *) (xr + u * 8 + 4);
-            v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-            if constexpr (NORM) {
-                const float4 ga = *(const float4 *) (g + u * 8), gb = *(const float4 *) (g + u * 8 + 4);
-                const float gg[8] = {ga.x, ga.y, ga.z, ga.w, gb.x, gb.y, gb.z, gb.w};
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float yn = v[e] * scale;     // ggml_vec_scale_f32 (ggml.c:6076)
-                    v[e] = gg[e] * yn;                 // ggml_mul(repeat(g), cur) (llama.cpp:984)
-                }
-            }
-        } else {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = 0.0f;
-        }
+    act_units<NORM>(x, g, N, K, [&](int t, int u, bool live, const float (&v)[8]) {
         float d, m;
         uint32_t qword;
         mv::q41_quad(v, d, m, qword);
         if (live) act41_emit(t, K / 32, u >> 2, u & 3, qword, d, m, xm, xs);
-    }
+    });
 }
 
 // pre-quantized Q4_1 blocks (ActQ: d, m + reference nibble qs) -> fragment and side images;
@@ -359,18 +258,13 @@ __global__ void k_mm41_images(const uint4 * __restrict__ nibi, const float * __r
     const long rb = idx >> 6;
     const int b = (int) (rb % nb), rt = (int) (rb / nb);
     const int row = rt * 32 + (lane & 31);
-    const size_t gbase = (((size_t) (row >> 3) * NC + (b >> 5)) * 4 + ((b & 31) >> 3)) * 64 + 8 * (row & 7);
     uint32_t field[8];                          // chain j: nibbles {2j, 2j+1, 16+2j, 17+2j}
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const uint4 v = nibi[gbase + j];
-        const uint32_t wd[4] = {v.x, v.y, v.z, v.w};
-        field[j] = (wd[(b & 7) >> 1] >> (16 * (b & 1))) & 0xFFFFu;
-    }
+    for (int j = 0; j < 8; ++j) field[j] = octet_chain_field(nibi, row, b, NC, j);
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         const uint32_t tf = field[2 * c + h];
-        a16[((((size_t) rt * nb + b) * 2 + (c >> 1)) * 64 + lane) * 2 + (c & 1)] =
+        a16[a16_slot(rt, nb, b, c, lane)] =
             make_uint2(h16(nib(tf, 0)) | h16(nib(tf, 2)) << 16, h16(nib(tf, 1)) | h16(nib(tf, 3)) << 16);
     }
     // group q = elements 8q..8q+7: the low (q < 2) or high (q >= 2) nibble pairs of chains 4(q&1)..+3
@@ -404,32 +298,20 @@ hipError_t launch_build_mm41(const QMatrix & w, void * a16, void * side, hipStre
 hipError_t mm_q41(const MmLaunch & L, int epi, hipStream_t s) {
     const QMatrix & w = L.w;
     Mm41Params P{};
-    if (epi == EPI_ROPE_KV) {
-        if (w.M != 3 * L.rk->E || L.rk->E % 32 || L.rk->hd % 4 || !L.rk->sp) return hipErrorInvalidValue;
-        P.rk = *L.rk;
-    }
     P.a16 = (const uint4 *) w.a16; P.side = (const uint4 *) w.side;
     P.xm = (const uint4 *) L.x.xm; P.xs = (const uint4 *) L.x.xs;
-    P.M = w.M; P.nb = w.K / 32; P.N = L.N; P.ntt = (L.N + TN - 1) / TN;
-    P.y = L.y; P.ldy = L.ldy; P.silu_tab = L.silu_tab;
-    const dim3 grid((w.M / TM) * P.ntt);
+    P.M = w.M; P.nb = w.K / 32;
+    P.o = mm_out(L, epi);
+    const dim3 grid((w.M / TM) * P.o.ntt);
     // LVK_MM41_DMA=0: the register-ring kernel instead of the LDS-DMA ring
     const char * dma_env = getenv("LVK_MM41_DMA");
     const bool dma = !dma_env || atoi(dma_env) != 0;
-#define LVK_MM41_GO(E)                                                                   \
-    do {                                                                                 \
-        if (dma) LVK_LAUNCH(k_mm_q41_dma<E>, grid, dim3(NT), LDS41, s, P);               \
-        else LVK_LAUNCH(k_mm_q41_mfma<E>, grid, dim3(NT), 0, s, P);                      \
-    } while (0)
-    switch (epi) {
-        case EPI_STORE: LVK_MM41_GO(EPI_STORE); break;
-        case EPI_RESID: LVK_MM41_GO(EPI_RESID); break;
-        case EPI_SWIGLU_F32: LVK_MM41_GO(EPI_SWIGLU_F32); break;
-        case EPI_ROPE_KV: LVK_MM41_GO(EPI_ROPE_KV); break;
-        default: return hipErrorNotSupported;
-    }
-#undef LVK_MM41_GO
-    return hipGetLastError();
+    return mm_epi_dispatch<Q4_1>(epi, [&](auto e) {
+        constexpr int E = decltype(e)::value;
+        if (dma) LVK_LAUNCH(k_mm_q41_dma<E>, grid, dim3(NT), LDS41, s, P);
+        else LVK_LAUNCH(k_mm_q41_mfma<E>, grid, dim3(NT), 0, s, P);
+        return hipGetLastError();
+    });
 }
 
 hipError_t act_q41(const float * x, const float * g, int N, int K, const ActImage & out, hipStream_t s) {

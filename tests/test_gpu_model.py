@@ -259,6 +259,33 @@ def test_mfma_prompt_13b_q4_1_shaped_vs_oracle(lvk, oracle, model_dir, monkeypat
     om.close()
 
 
+@pytest.mark.parametrize("rope", ["1", "0"])
+def test_mfma_prompt_q4_1_register_ring_vs_oracle(lvk, oracle, tiny_models, monkeypatch, rope):
+    """the Q4_1 register-ring matmul (LVK_MM41_DMA=0) in every role of a layer: QKV with the RoPE +
+    KV epilogue (default) or a plain store (LVK_MM_ROPE=0), Wo / W2 with the residual add, W1|W3
+    with SwiGLU -- the op-level test reaches that kernel with the plain store only.  The tiny
+    Q4_1 model (n_embd 256: 2 to 12 row tiles per matrix), a 33-token prompt (ragged last token
+    tile), then a decode step on the KV cache it wrote, bit-exact against the oracle"""
+    path = tiny_models["tiny_q4_1"]
+    monkeypatch.setenv("LVK_MM41_DMA", "0")
+    monkeypatch.setenv("LVK_MM_ROPE", rope)
+    m = lvk.Llama(path, n_ctx=256)
+    om = oracle.model(path, 256)
+    toks = np.array([1] + [100 + (i * 7919) % 31000 for i in range(1, 33)], np.int32)
+    m.set_profiling(True)
+    m.reset_profile()
+    a = m.eval(toks, 0)
+    # the MFMA path ran: per layer the activation image and the matmul (+ k_rope_kv) in the QKV class
+    assert m.profile()["qkv"]["launches"] == 40 * (2 if rope == "1" else 3)
+    m.set_profiling(False)
+    b = om.eval(toks, 0)
+    assert np.array_equal(bits(a), bits(b))
+    tok = int(np.argmax(b[-1]))
+    assert np.array_equal(bits(m.eval([tok], len(toks))), bits(om.eval([tok], len(toks))))
+    m.close()
+    om.close()
+
+
 # ---------------------------------------------------------------------------
 # LLaMA-65B layer shapes (n_embd 8192, 64 heads, n_ff 22016; llama.cpp:771-778):
 # the decode kernels compiled for K = 8192 / 22016, the 64-head attention grid
