@@ -59,7 +59,7 @@ LLAMA_API bool llama_mmap_supported(void);                                    /*
 LLAMA_API bool llama_mlock_supported(void);                                   /* llama.h:71 */
 
 /* llama.h:74-76: load a ggml / ggmf / ggjt model into HBM; NULL on failure (error printed).
- * The matrices are all f16, all Q4_0 or all Q4_1 (mixed files and f32 matrices are refused). */
+ * The matrices are all f32, all f16, all Q4_0 or all Q4_1 (mixed files are refused). */
 LLAMA_API struct llama_context * llama_init_from_file(const char * path_model, struct llama_context_params params);
 /* llama.h:79 */
 LLAMA_API void llama_free(struct llama_context * ctx);

@@ -59,6 +59,15 @@ LVK_API int lvk_mul_mat_q_mfma(int type, const void * w, int m, int k, const flo
 LVK_API int lvk_mul_mat_f16(const uint16_t * w, int m, int k, const float * g, const float * x, int n, float * y,
                             int kernel);
 
+/* f32 weights (ggml type 0): y[t][r] = ggml_vec_dot_f32(k, w_r, a[t]) with a = x, or
+ * a = g * rms_norm(x) when g != NULL, exactly as ggml_compute_forward_mul_mat_f32 (AVX2)
+ * computes it.  w: m rows of k f32 values in file layout; k % 256 == 0, any m >= 1, n >= 1.
+ * kernel: 0 = the kernel a context would choose (n == 1: the decode matvec, else the batched
+ * matmul), 1 = the decode matvec (matvec_f32.hip, n == 1 only), 2 = the batched matmul on the
+ * f32 matrix cores (mm_f32.hip).  Any other combination returns nonzero. */
+LVK_API int lvk_mul_mat_f32(const float * w, int m, int k, const float * g, const float * x, int n, float * y,
+                            int kernel);
+
 /* one layer's attention block on an f16 KV cache (llama.cpp:1010-1061):
  * kc [n_ctx][n_embd] f16, vc [n_embd][n_ctx] f16, q [n][n_embd] f32 (post-RoPE)
  * -> out [n][n_embd] f32 (merged heads, before the Wo quantization) */

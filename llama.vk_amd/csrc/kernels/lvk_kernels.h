@@ -37,8 +37,9 @@ struct EventSplit {
             hipLaunchKernelGGL(kern, grid, block, lds, stream, __VA_ARGS__);                                   \
     } while (0)
 
-// = the model file's tensor type ids; F16 matrices use the paired-step octet image below
-enum QType : int { F16 = 1, Q4_0 = 2, Q4_1 = 3 };
+// = the model file's tensor type ids; F16 matrices use the paired-step octet image below, F32
+// matrices the step octet image
+enum QType : int { F32 = 0, F16 = 1, Q4_0 = 2, Q4_1 = 3 };
 
 // error word: kernels whose workgroups wait on each other spin with a bound; a
 // spin that gives up stores one of these into the context's host-mapped error
@@ -56,6 +57,8 @@ enum DevError : unsigned { LVK_ERR_NONE = 0, LVK_ERR_ATTN_SPIN = 1, LVK_ERR_DECO
 // row is zero-padded to 32 blocks when K % 1024 != 0 and never streamed).
 // F16 matrices: nib is the paired-step octet image [ceil(M/8)][K/64][64] uint4
 // (f16_common.h; f16_image_bytes, launch_repack_f16), scl is unused.
+// F32 matrices: nib is the step octet image [ceil(M/8)][K/32][64] uint4 (f32_common.h;
+// f32_image_bytes, launch_repack_f32), scl is unused.
 struct QMatrix {
     int qtype = Q4_0;
     int M = 0, K = 0;
@@ -122,7 +125,7 @@ struct MvLaunch {
     float * u = nullptr;                   // EPI_SWIGLU_F32: u in f32 [N][M/2]
 };
 
-// dispatches on L.w.qtype: Q4_0 here (matvec_q4.hip), Q4_1 and F16 forwarded.  Every matvec
+// dispatches on L.w.qtype: Q4_0 here (matvec_q4.hip), Q4_1, F16 and F32 forwarded.  Every matvec
 // launcher returns hipErrorNotSupported for a (pro, epi) pair it has no instantiation for and
 // hipErrorInvalidValue when the input that pro reads (x, g, or xq.qs / xq.d / xq.m) is null.
 hipError_t launch_matvec(const MvLaunch & L, int pro, int epi, hipStream_t s);
@@ -130,8 +133,8 @@ hipError_t launch_matvec(const MvLaunch & L, int pro, int epi, hipStream_t s);
 hipError_t launch_matvec_q41(const MvLaunch & L, int pro, int epi, hipStream_t s);
 
 // single-token decode matvec, one workgroup per CU (matvec_cu.hip for Q4_0,
-// matvec_cu41.hip for Q4_1; F16 has one single-token kernel, matvec_f16.hip, for every row
-// length).  Row lengths compiled in: matvec_cu_supported(K, qtype).
+// matvec_cu41.hip for Q4_1; F16 and F32 have one single-token kernel each, matvec_f16.hip and
+// matvec_f32.hip, for every row length).  Row lengths compiled in: matvec_cu_supported(K, qtype).
 // Returns hipErrorNotSupported for anything else (the caller then uses launch_matvec).
 bool matvec_cu_supported(int K, int qtype = Q4_0);
 hipError_t launch_matvec_cu(const MvLaunch & L, int pro, int epi, hipStream_t s);
@@ -212,16 +215,19 @@ inline const uint4 * q41_wsum(const QMatrix & w) {
 }
 
 // ---------------------------------------------------------------------------
-// Batched (N > 1) matmul, bit-exact like launch_matvec.  One interface for the three
+// Batched (N > 1) matmul, bit-exact like launch_matvec.  One interface for the four
 // weight types; launch_mm (mm_launch.hip) dispatches on w.qtype:
 //   Q4_0 (mm_mfma.hip): the matrix cores produce the per-chain integer partials, the VALU
 //     runs the reference fp32 chains.  Weights: the octet image, or QMatrix::a16 when built.
 //   Q4_1 (mm_mfma41.hip): the matrix cores also produce the cross-term sums and the scale
 //     products.  Weights: QMatrix::a16 + QMatrix::side, both from launch_build_mm41.
 //   F16 (mm_f16.hip): the fp32 chains of matvec_f16.hip, tiled over tokens.
+//   F32 (mm_f32.hip): the f32 matrix cores run the reference's fp32 chains themselves.
 // The activations reach the kernels as an operand image of the weight type:
 //   xm : Q4_0 / Q4_1 the masked MFMA B-fragment image (mm_common.h xm_slot);
-//        F16 the paired-step f16 rows, N rounded up to MM_F16_TPAD rows
+//        F16 the paired-step f16 rows, N rounded up to MM_F16_TPAD rows;
+//        F32 plain f32 rows [N][K] -- any such rows serve as the image, so a caller whose
+//        input needs no RMSNorm points xm at it instead of calling launch_act
 //   da : Q4_0 the block scales [N][K/32]
 //   xs : Q4_1 the side image [N/16][K/32][64] x 16 B (mm_common.h act41_emit)
 // xm must be ZEROED once at allocation: the writers only ever store the active fragment
@@ -238,13 +244,14 @@ constexpr int MM_TN = 16;          // tokens per MFMA tile
 constexpr int MM_F16_TPAD = 32;    // the widest token tile of mm_f16.hip
 inline ActImageBytes act_image_bytes(int qtype, int N, int K) {
     if (qtype == F16) return {(size_t) ((N + MM_F16_TPAD - 1) / MM_F16_TPAD * MM_F16_TPAD) * K * 2, 0, 0};
+    if (qtype == F32) return {(size_t) N * K * 4, 0, 0};
     const size_t tiles = (size_t) (N + MM_TN - 1) / MM_TN, nb = (size_t) K / 32;
     return {tiles * nb * 4 * 64 * 8, qtype == Q4_0 ? (size_t) N * nb * 4 : 0, qtype == Q4_1 ? tiles * nb * 64 * 16 : 0};
 }
 // f32 rows x[N][K] (rms_norm * g when g != nullptr) -> the operand image: quantize_row_q4_0 /
-// quantize_row_q4_1 (AVX2 branches) or f32 -> f16 RNE
+// quantize_row_q4_1 (AVX2 branches), f32 -> f16 RNE, or (F32) the f32 rows themselves
 hipError_t launch_act(int qtype, const float * x, const float * g, int N, int K, const ActImage & out, hipStream_t s);
-// pre-quantized blocks (ActQ of the same type) -> the operand image; F16: hipErrorNotSupported
+// pre-quantized blocks (ActQ of the same type) -> the operand image; F16 / F32: hipErrorNotSupported
 hipError_t launch_actq_to_image(int qtype, const ActQ & q, int N, int K, const ActImage & out, hipStream_t s);
 
 // EPI_ROPE_KV: RoPE + KV append in the QKV matmul's epilogue (f16 KV cache): the f32 Q|K|V
@@ -270,7 +277,7 @@ struct MmLaunch {
 // which epilogues a type's kernels implement; launch_mm returns hipErrorNotSupported for the others
 constexpr bool mm_epi_supported(int qtype, int epi) {
     switch (epi) {
-        case EPI_STORE: case EPI_RESID: case EPI_SWIGLU_F32: return qtype == F16 || qtype == Q4_0 || qtype == Q4_1;
+        case EPI_STORE: case EPI_RESID: case EPI_SWIGLU_F32: return qtype == F32 || qtype == F16 || qtype == Q4_0 || qtype == Q4_1;
         case EPI_ROPE_KV: return qtype == Q4_0 || qtype == Q4_1;
         case EPI_SWIGLU_Q: return qtype == Q4_0;
     }
@@ -284,11 +291,13 @@ hipError_t launch_mm(const MmLaunch & L, int epi, hipStream_t s);
 hipError_t act_q40(const float * x, const float * g, int N, int K, const ActImage & out, hipStream_t s);
 hipError_t act_q41(const float * x, const float * g, int N, int K, const ActImage & out, hipStream_t s);
 hipError_t act_f16(const float * x, const float * g, int N, int K, const ActImage & out, hipStream_t s);
+hipError_t act_f32(const float * x, const float * g, int N, int K, const ActImage & out, hipStream_t s);
 hipError_t actq_image_q40(const ActQ & q, int N, int K, const ActImage & out, hipStream_t s);
 hipError_t actq_image_q41(const ActQ & q, int N, int K, const ActImage & out, hipStream_t s);
 hipError_t mm_q40(const MmLaunch & L, int epi, hipStream_t s);
 hipError_t mm_q41(const MmLaunch & L, int epi, hipStream_t s);
 hipError_t mm_f16(const MmLaunch & L, int epi, hipStream_t s);
+hipError_t mm_f32(const MmLaunch & L, int epi, hipStream_t s);
 
 // the f16 A-fragment image of a Q4_0 matrix (QMatrix::a16): bytes, and its build from the
 // matrix's octet image (M % 32 == 0)
@@ -318,6 +327,14 @@ hipError_t launch_repack_f16(const void * src_rows, int M, int K, uint4 * img, h
 // (f32 -> f16) of the f32 row L.x; EPI_STORE, EPI_RESID, EPI_QKV, EPI_SWIGLU_F32.
 // launch_matvec and launch_matvec_cu forward here
 hipError_t launch_matvec_f16(const MvLaunch & L, int pro, int epi, hipStream_t s);
+
+// f32 weights (type 0).  Image: 4 B per weight, rows padded to a multiple of 8.
+inline size_t f32_image_bytes(int M, int K) { return (size_t) ((M + 7) / 8 * 8) * K * 4; }
+hipError_t launch_repack_f32(const void * src_rows, int M, int K, uint4 * img, hipStream_t s, int interleave4 = 0);
+// single-token decode matvec (matvec_f32.hip): PRO_NORM (rms_norm * g) or PRO_ACTF of the f32
+// row L.x, used as it is; EPI_STORE, EPI_RESID, EPI_QKV, EPI_SWIGLU_F32.
+// launch_matvec and launch_matvec_cu forward here
+hipError_t launch_matvec_f32(const MvLaunch & L, int pro, int epi, hipStream_t s);
 
 // operator-level helpers used by the C ABI tests
 hipError_t launch_quantize_act(const float * x, int N, int K, int qtype, ActQ out, hipStream_t s);

@@ -421,13 +421,14 @@ void * lvk_probe_trace() { void * p = nullptr; (void) hipGetSymbolAddress(&p, HI
 // n_ff 11008 / 22016; llama.cpp:771-779)
 bool matvec_cu_supported(int K, int qtype) {
     if (qtype == Q4_1) return matvec_cu41_supported(K);
-    if (qtype == F16) return true;      // matvec_f16.hip takes every row length
+    if (qtype == F16 || qtype == F32) return true;      // matvec_f16.hip / matvec_f32.hip take every row length
     return K == 4096 || K == 11008 || K == 8192 || K == 22016;
 }
 
 hipError_t launch_matvec_cu(const MvLaunch & L, int pro, int epi, hipStream_t s) {
     if (L.w.qtype == Q4_1) return launch_matvec_cu41(L, pro, epi, s);
     if (L.w.qtype == F16) return launch_matvec_f16(L, pro, epi, s);
+    if (L.w.qtype == F32) return launch_matvec_f32(L, pro, epi, s);
     if (L.w.qtype != Q4_0 || L.n_tokens != 1 || L.w.M % 8) return hipErrorNotSupported;
     if (!mv_inputs_set(L, pro)) return hipErrorInvalidValue;
     CuParams P{};

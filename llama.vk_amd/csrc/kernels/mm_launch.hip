@@ -1,6 +1,6 @@
 // mm_launch.hip -- the batched (N > 1) matmul interface of lvk_kernels.h: the weight-type
 // dispatch of launch_act / launch_actq_to_image / launch_mm with the checks every type shares
-// (the kernels are in mm_mfma.hip Q4_0, mm_mfma41.hip Q4_1, mm_f16.hip F16), and the unfused
+// (the kernels are in mm_mfma.hip Q4_0, mm_mfma41.hip Q4_1, mm_f16.hip F16, mm_f32.hip F32), and the unfused
 // RoPE + KV append of stored Q|K|V rows.
 #include "mm_common.h"
 
@@ -14,7 +14,7 @@ bool mm_supported(const QMatrix & w) {
     switch (w.qtype) {
         case Q4_0: return w.M % MM_TM == 0 && w.K % 256 == 0;
         case Q4_1: return w.a16 && w.side && w.M % MM_TM == 0 && w.K % 256 == 0;
-        case F16: return w.M >= 1 && w.K % 256 == 0;
+        case F16: case F32: return w.M >= 1 && w.K % 256 == 0;
     }
     return false;
 }
@@ -25,6 +25,7 @@ hipError_t launch_act(int qtype, const float * x, const float * g, int N, int K,
         case Q4_0: return act_q40(x, g, N, K, out, s);
         case Q4_1: return act_q41(x, g, N, K, out, s);
         case F16: return act_f16(x, g, N, K, out, s);
+        case F32: return act_f32(x, g, N, K, out, s);
     }
     return hipErrorNotSupported;
 }
@@ -45,7 +46,8 @@ hipError_t launch_mm(const MmLaunch & L, int epi, hipStream_t s) {
     switch (w.qtype) {
         case Q4_0: return mm_q40(L, epi, s);
         case Q4_1: return mm_q41(L, epi, s);
-        default: return mm_f16(L, epi, s);
+        case F16: return mm_f16(L, epi, s);
+        default: return mm_f32(L, epi, s);
     }
 }
 

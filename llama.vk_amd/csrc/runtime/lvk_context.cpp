@@ -127,8 +127,8 @@ void Context::init(const llama_context_params & p) {
         img = alloc_image(std::max(E, F));
         const char * sq = getenv("LVK_MM_SWIGLU_Q");
         if (mm_epi_supported(model.qtype, EPI_SWIGLU_Q) && (!sq || atoi(sq) != 0)) img_w2 = alloc_image(F);
-        // f16 weights take the Wo input in f32; the Q4 types take the quantized aq_attn
-        if (model.qtype == F16) attn_f32 = (float *) model.alloc(C * E * 4);
+        // f16 and f32 weights take the Wo input in f32; the Q4 types take the quantized aq_attn
+        if (model.qtype == F16 || model.qtype == F32) attn_f32 = (float *) model.alloc(C * E * 4);
         qkv32 = (float *) model.alloc(C * 3 * E * 4);
         uf = (float *) model.alloc(C * F * 4);
         prompt_exact = getenv("LVK_PROMPT_EXACT") && atoi(getenv("LVK_PROMPT_EXACT")) != 0;
@@ -234,14 +234,16 @@ void Context::collect_profile() {
 
 static double qbytes(const QMatrix & w) {
     if (w.qtype == F16) return (double) w.M * w.K * 2;
+    if (w.qtype == F32) return (double) w.M * w.K * 4;
     return (double) w.M * (w.K / 32) * (w.qtype == Q4_0 ? 20 : 24);
 }
 
 // batches go through the batched matmuls (launch_act + launch_mm) when every matrix of the
-// model fits them: f16 weights from 2 tokens on (their matvec is single-token only), the Q4
+// model fits them: f16 and f32 weights from 2 tokens on (their matvec is single-token only), the Q4
 // types from 16 (the MFMA tile is 16 tokens wide; below that the per-row VALU kernels win)
 bool Context::use_batched(int n) const {
-    if (n == 1 || (model.qtype != F16 && (n < 16 || prompt_exact))) return false;
+    const bool q4 = model.qtype == Q4_0 || model.qtype == Q4_1;
+    if (n == 1 || (q4 && (n < 16 || prompt_exact))) return false;
     for (const Layer & ly : model.layers)
         if (!mm_supported(ly.wqkv) || !mm_supported(ly.wo) || !mm_supported(ly.w13) || !mm_supported(ly.w2))
             return false;
@@ -250,7 +252,8 @@ bool Context::use_batched(int n) const {
 
 // The layer sequence, the same for every weight type (f16 weights:
 // ggml_compute_forward_mul_mat_f16_f32 where the Q4 types run mul_mat_q_f32; the activations are
-// converted to f16 where the Q4 types quantize them):
+// converted to f16 where the Q4 types quantize them; f32 weights: ggml_compute_forward_mul_mat_f32
+// on the f32 rows as they are):
 //   embed, then per layer norm -> QKV, RoPE + KV append, attention, Wo (+x),
 //   norm -> W1|W3 (SwiGLU), W2 (+x), then the head.
 // Batches (use_batched) run it as operand image + matmul per matrix, everything else as one
@@ -272,9 +275,16 @@ void Context::enqueue_forward(int n, bool last_only, const int * tok_src, int lo
         timed_launch(K_EMBED, 0, [&] {
             return launch_embed(model.tok_emb, model.emb_type, E, n == 1 ? &sp_d->pad0 : tok_src, n, x, stream);
         });
-    // x[n][K] (rms_norm * g when g) -> img, and y = / += W img
-    auto act = [&](int cls, const float * xin, const float * g, int K) {
+    // x[n][K] (rms_norm * g when g) -> img, and y = / += W img.  f32 weights read f32 rows:
+    // without a norm the input itself is the image
+    auto act = [&](int cls, const float * xin, const float * g, int K) -> ActImage {
+        if (qt == F32 && !g) {
+            ActImage in;
+            in.xm = (void *) xin;
+            return in;
+        }
         timed_launch(cls, 0, [&] { return launch_act(qt, xin, g, n, K, img, stream); });
+        return img;
     };
     auto mm = [&](int cls, const QMatrix & w, const ActImage & in, float * y, int ldy, int epi, const RopeKV * rk = nullptr,
                   const ActImage & out = {}) {
@@ -288,22 +298,22 @@ void Context::enqueue_forward(int n, bool last_only, const int * tok_src, int lo
         const Layer & ly = model.layers[il];
         uint16_t * kcl = kc_layer(il);
         uint16_t * vcl = vc_layer(il);
-        // every attention kernel writes the Wo input quantized (aq_attn; Q4_0 blocks for an f16
-        // model, which reads attn_f32 instead)
-        AttnLaunch at{q16, kcl, vcl, scores, aq_attn, qt == F16 ? Q4_0 : qt, exp_tab, sp_d, n, E, H, n_ctx};
+        // every attention kernel writes the Wo input quantized (aq_attn; Q4_0 blocks for an f16 or
+        // f32 model, which reads attn_f32 instead)
+        AttnLaunch at{q16, kcl, vcl, scores, aq_attn, qt == F16 || qt == F32 ? Q4_0 : qt, exp_tab, sp_d, n, E, H, n_ctx};
         at.out_f32 = attn_f32;
         at.exp_computed = exp_computed;
         at.err = err_d;
         at.kv32 = kv32;
         at.seq_epochs = seq_epochs ? 1 : 0;
         if (batched) {
-            act(K_QKV, x, ly.attn_norm, E);
+            ActImage in = act(K_QKV, x, ly.attn_norm, E);
             if (!kv32 && mm_rope_fused && mm_epi_supported(qt, EPI_ROPE_KV)) {
                 // RoPE + KV append in the matmul's epilogue (the f32 rows never reach memory)
                 const RopeKV rk{rope, sp_d, n_ctx, E, hd, q16, kcl, vcl};
-                mm(K_QKV, ly.wqkv, img, nullptr, 0, EPI_ROPE_KV, &rk);
+                mm(K_QKV, ly.wqkv, in, nullptr, 0, EPI_ROPE_KV, &rk);
             } else {
-                mm(K_QKV, ly.wqkv, img, qkv32, 3 * E, EPI_STORE);
+                mm(K_QKV, ly.wqkv, in, qkv32, 3 * E, EPI_STORE);
                 timed_launch(K_QKV, 0, [&] {
                     return launch_rope_kv(qkv32, n, E, hd, rope, sp_d, n_ctx, q16, kcl, vcl, stream, kv32);
                 });
@@ -317,18 +327,19 @@ void Context::enqueue_forward(int n, bool last_only, const int * tok_src, int lo
                 });
             else
                 timed_launch(K_ATTN, 0, [&] { return launch_attention(at, stream); });
-            if (attn_f32) act(K_WO, attn_f32, nullptr, E);
+            in = img;
+            if (attn_f32) in = act(K_WO, attn_f32, nullptr, E);
             else if (!wo_fused) timed_launch(K_WO, 0, [&] { return launch_actq_to_image(qt, aq_attn, n, E, img, stream); });
-            mm(K_WO, ly.wo, img, x, E, EPI_RESID);
-            act(K_W13, x, ly.ffn_norm, E);
+            mm(K_WO, ly.wo, in, x, E, EPI_RESID);
+            in = act(K_W13, x, ly.ffn_norm, E);
             if (img_w2.xm) {
                 // SwiGLU + the W2 input's quantization in the W1|W3 epilogue
-                mm(K_W13, ly.w13, img, nullptr, 0, EPI_SWIGLU_Q, nullptr, img_w2);
+                mm(K_W13, ly.w13, in, nullptr, 0, EPI_SWIGLU_Q, nullptr, img_w2);
                 mm(K_W2, ly.w2, img_w2, x, E, EPI_RESID);
             } else {
-                mm(K_W13, ly.w13, img, uf, F, EPI_SWIGLU_F32);
-                act(K_W2, uf, nullptr, F);
-                mm(K_W2, ly.w2, img, x, E, EPI_RESID);
+                mm(K_W13, ly.w13, in, uf, F, EPI_SWIGLU_F32);
+                in = act(K_W2, uf, nullptr, F);
+                mm(K_W2, ly.w2, in, x, E, EPI_RESID);
             }
             continue;
         }
@@ -362,8 +373,8 @@ void Context::enqueue_forward(int n, bool last_only, const int * tok_src, int lo
     if (!model.has_head || !head) return;   // not the last pipeline stage: x is the output
     if (batched && !last_only && mm_supported(model.output)) {
         // logits_all: lm_head over every row
-        act(K_LMHEAD, x, model.norm, E);
-        mm(K_LMHEAD, model.output, img, logits_out, V, EPI_STORE);
+        const ActImage in = act(K_LMHEAD, x, model.norm, E);
+        mm(K_LMHEAD, model.output, in, logits_out, V, EPI_STORE);
     } else {
         MvLaunch o;
         o.w = model.output; o.x = x; o.g = model.norm; o.sp = sp_d; o.y = logits_out;

@@ -110,8 +110,9 @@ struct Context {
     // prompt: RoPE + KV append fused into the QKV matmul (LVK_MM_ROPE=0: separate kernel)
     bool mm_rope_fused = [] { const char * e = getenv("LVK_MM_ROPE"); return !e || atoi(e) != 0; }();
     float * uf = nullptr;        // [C][F] silu(w1 x) * (w3 x)
-    // f16 models (model.qtype == F16) only: the attention's f32 output, the Wo input (converted
-    // to f16 by launch_act / the matvec's prologue); nullptr = Wo takes the quantized aq_attn
+    // f16 and f32 models only: the attention's f32 output, the Wo input (F16: converted to f16
+    // by launch_act / the matvec's prologue; F32: read as it is); nullptr = Wo takes the
+    // quantized aq_attn
     float * attn_f32 = nullptr;  // [C][E]
 
     // decode graph (N = 1, last-token logits)

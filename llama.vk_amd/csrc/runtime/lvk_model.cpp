@@ -245,11 +245,13 @@ void load_model(Model & m, const std::string & path, bool vocab_only, hipStream_
     Tensor t_tok = get("tok_embeddings.weight", {E, V});
     Tensor t_norm = get("norm.weight", {E});
     Tensor t_out = get("output.weight", {E, V});
-    if (t_out.type != 1 && t_out.type != 2 && t_out.type != 3)
-        throw Error("llama.vk_amd: output.weight must be f16, Q4_0 or Q4_1");
+    if (t_out.type > 3)
+        throw Error("llama.vk_amd: output.weight must be f32, f16, Q4_0 or Q4_1");
     m.qtype = (int) t_out.type;
     if (m.qtype == F16 && t_tok.type != 1)
         throw Error("llama.vk_amd: tok_embeddings.weight of an f16 model must be f16 (mixed files are not supported)");
+    if (m.qtype == F32 && t_tok.type != 0)
+        throw Error("llama.vk_amd: tok_embeddings.weight of an f32 model must be f32 (mixed files are not supported)");
     const size_t rb_E = type_row_bytes(m.qtype, E), rb_F = type_row_bytes(m.qtype, F);
     size_t stage_n = std::max({t_out.size, 3 * E * rb_E, 2 * (size_t) F * rb_E, (size_t) E * rb_F});
     void * stage = nullptr;
@@ -279,6 +281,11 @@ void load_model(Model & m, const std::string & path, bool vocab_only, hipStream_
             m.weight_bytes += (size_t) M * K * 2;
             return q;
         }
+        if (m.qtype == F32) {
+            q.nib = (const uint4 *) m.alloc(f32_image_bytes(M, K));
+            m.weight_bytes += (size_t) M * K * 4;
+            return q;
+        }
         const size_t nib = qimage_nib_bytes(M, K);
         const size_t scl = qimage_scl_bytes(M, K, m.qtype);
         q.nib = (const uint4 *) m.alloc(nib);
@@ -286,7 +293,8 @@ void load_model(Model & m, const std::string & path, bool vocab_only, hipStream_
         m.weight_bytes += (size_t) M * (K / 32) * (m.qtype == Q4_0 ? 20 : 24);
         return q;
     };
-    // Q4 models only (an f16 model's prompt matmul, mm_f16.hip, streams the decode image): the
+    // Q4 models only (an f16 or f32 model's prompt matmul, mm_f16.hip / mm_f32.hip, streams the
+    // decode image): the
     // prompt matmul's f16 A-fragment images (mm_mfma.hip, 2 B per weight: 13.2 GB for
     // 7B, 130 GB for 65B), decided by capacity (the A-image table):
     //   * Q4_1: the f16 image plus the per-block side image (mm_mfma41.hip, 3 B per weight in
@@ -298,7 +306,7 @@ void load_model(Model & m, const std::string & path, bool vocab_only, hipStream_
     //     most a quarter of the device's memory: 7B / 13B-shaped models and every stage of a
     //     65B split over 8 GPUs, not the whole 65B on one GPU (130 GB of 288 GB);
     //     LVK_PROMPT_A16=1 builds it whenever it fits, =0 never
-    bool a16 = m.qtype != F16 && prompt_a16_env();
+    bool a16 = m.qtype != F16 && m.qtype != F32 && prompt_a16_env();
     if (a16) {
         const size_t EE = (size_t) E * E, EF = (size_t) E * F;
         const size_t per_w = m.qtype == Q4_0 ? 2 : 3;
@@ -310,8 +318,8 @@ void load_model(Model & m, const std::string & path, bool vocab_only, hipStream_
         if (a16 && m.qtype == Q4_0 && !prompt_a16_forced()) a16 = need <= total_b / 4;
     }
     auto repack = [&](QMatrix & q, int interleave4 = 0) {
-        if (q.qtype == F16) {
-            LVK_HIP(launch_repack_f16(stage, q.M, q.K, (uint4 *) q.nib, s, interleave4));
+        if (q.qtype == F16 || q.qtype == F32) {
+            LVK_HIP((q.qtype == F16 ? launch_repack_f16 : launch_repack_f32)(stage, q.M, q.K, (uint4 *) q.nib, s, interleave4));
             LVK_HIP(hipStreamSynchronize(s));
             return;
         }
@@ -330,7 +338,7 @@ void load_model(Model & m, const std::string & path, bool vocab_only, hipStream_
     };
     auto check_q = [&](const Tensor & t, const std::string & name) {
         if ((int) t.type != m.qtype)
-            throw Error("llama.vk_amd: tensor '" + name + "' is not in the model's weight format (mixed f16 / Q4 files are not supported)");
+            throw Error("llama.vk_amd: tensor '" + name + "' is not in the model's weight format (mixed f32 / f16 / Q4 files are not supported)");
     };
 
     // embeddings stay in file layout (gathered by row, ggml.c:6868-6895)

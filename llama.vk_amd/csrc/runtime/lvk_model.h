@@ -54,7 +54,7 @@ struct Layer {
 struct Model {
     HParams hp;
     Vocab vocab;
-    int qtype = Q4_0;              // weight format of the layer matrices and lm_head: F16, Q4_0 or Q4_1
+    int qtype = Q4_0;              // weight format of the layer matrices and lm_head: F32, F16, Q4_0 or Q4_1
     int emb_type = Q4_0;           // tok_embeddings storage type (ggjt ftype id)
     void * tok_emb = nullptr;      // device, file layout
     float * norm = nullptr;        // [E]

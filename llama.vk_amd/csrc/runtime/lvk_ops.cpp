@@ -132,11 +132,15 @@ static void mm_batched(Dev & dv, const lvk::QMatrix & q, const float * xd, const
     const lvk::ActImageBytes nbytes = lvk::act_image_bytes(q.qtype, n, q.K);
     lvk::MmLaunch L;
     L.w = q; L.N = n; L.y = yd; L.ldy = q.M;
-    L.x.xm = dv.get(nbytes.xm);
-    LVK_HIP(hipMemset(L.x.xm, 0, nbytes.xm));
-    if (nbytes.da) L.x.da = (float *) dv.get(nbytes.da);
-    if (nbytes.xs) L.x.xs = dv.get(nbytes.xs);
-    LVK_HIP(lvk::launch_act(q.qtype, xd, gd, n, q.K, L.x, nullptr));
+    if (q.qtype == lvk::F32 && !gd) {
+        L.x.xm = (void *) xd;           // f32 weights read the f32 rows in place
+    } else {
+        L.x.xm = dv.get(nbytes.xm);
+        LVK_HIP(hipMemset(L.x.xm, 0, nbytes.xm));
+        if (nbytes.da) L.x.da = (float *) dv.get(nbytes.da);
+        if (nbytes.xs) L.x.xs = dv.get(nbytes.xs);
+        LVK_HIP(lvk::launch_act(q.qtype, xd, gd, n, q.K, L.x, nullptr));
+    }
     LVK_HIP(lvk::launch_mm(L, lvk::EPI_STORE, nullptr));
 }
 
@@ -188,6 +192,33 @@ int lvk_mul_mat_f16(const uint16_t * w, int m, int k, const float * g, const flo
             lvk::MvLaunch L;
             L.w = q; L.x = xd; L.g = gd; L.sp = dv.up(&sp, 1); L.y = yd;
             LVK_HIP(lvk::launch_matvec_f16(L, g ? lvk::PRO_NORM : lvk::PRO_ACTF, lvk::EPI_STORE, nullptr));
+        } else {
+            mm_batched(dv, q, xd, gd, n, yd);
+        }
+        LVK_HIP(hipMemcpy(y, yd, (size_t) n * m * 4, hipMemcpyDeviceToHost));
+        return 0;
+    } catch (const lvk::Error & e) { return fail(__func__, e.msg); }
+}
+
+int lvk_mul_mat_f32(const float * w, int m, int k, const float * g, const float * x, int n, float * y, int kernel) {
+    try {
+        if (!w || !x || !y || m < 1 || n < 1 || k < 256 || k % 256) return fail(__func__, "need m >= 1, n >= 1, k % 256 == 0");
+        if (kernel < 0 || kernel > 2 || (kernel == 1 && n != 1)) return fail(__func__, "kernel: 0 auto, 1 decode matvec (n == 1), 2 batched");
+        if (kernel == 0) kernel = n == 1 ? 1 : 2;
+        Dev dv;
+        const float * wd = dv.up(w, (size_t) m * k);
+        lvk::QMatrix q;
+        q.qtype = lvk::F32; q.M = m; q.K = k;
+        q.nib = (const uint4 *) dv.get(lvk::f32_image_bytes(m, k));
+        LVK_HIP(lvk::launch_repack_f32(wd, m, k, (uint4 *) q.nib, nullptr));
+        float * xd = dv.up(x, (size_t) n * k);
+        const float * gd = g ? dv.up(g, (size_t) k) : nullptr;
+        float * yd = (float *) dv.get((size_t) n * m * 4);
+        if (kernel == 1) {
+            lvk::StepParams sp{0, 1, 0, 0};
+            lvk::MvLaunch L;
+            L.w = q; L.x = xd; L.g = gd; L.sp = dv.up(&sp, 1); L.y = yd;
+            LVK_HIP(lvk::launch_matvec_f32(L, g ? lvk::PRO_NORM : lvk::PRO_ACTF, lvk::EPI_STORE, nullptr));
         } else {
             mm_batched(dv, q, xd, gd, n, yd);
         }

@@ -1,4 +1,4 @@
-// lvk-gen-model: seeded synthetic LLaMA model writer (ggjt v1, f16 / Q4_0 / Q4_1).
+// lvk-gen-model: seeded synthetic LLaMA model writer (ggjt v1, f32 / f16 / Q4_0 / Q4_1).
 //
 // There are no real checkpoints anywhere in this environment, so every parity
 // and performance input is a synthetic ggjt v1 file with the tensor names,
@@ -15,11 +15,14 @@
 //             scale s, so the values spread like the Q4 ones but carry full random 10-bit
 //             mantissas; one element in 256 is a special: +0, -0 or an f16 subnormal with
 //             random mantissa and sign.  1-D tensors stay f32.
+//   f32     : (--ftype 0) the f16 recipe without the rounding: element = (16 U1 - 8) * (0.5 + U2)
+//             * s at full f32 precision; one element in 256 is a special: +0, -0 or an f32
+//             subnormal with random mantissa and sign.  Header ftype 0.
 //   norms   : 1 + 0.1 * N(0,1)   (Irwin-Hall approximation of N(0,1))
 //   vocab   : copied from a ggjt vocab section file, or synthetic tokens.
 //
 // usage: lvk-gen-model OUT --n-embd 4096 --n-head 32 --n-layer 32
-//                      [--n-mult 256] [--n-vocab 32000] [--ftype 1|2|3]
+//                      [--n-mult 256] [--n-vocab 32000] [--ftype 0|1|2|3]
 //                      [--seed 1] [--vocab tests/golden/vocab32000.bin]
 #include <cmath>
 #include <cstdint>
@@ -123,12 +126,38 @@ void fill_f16(uint16_t * out, uint64_t n, float s, const Gen & g, uint32_t ti) {
     for (auto & t : th) t.join();
 }
 
+// fill `out` with `n` f32 elements of a tensor; parallel over elements
+void fill_f32(uint32_t * out, uint64_t n, float s, const Gen & g, uint32_t ti) {
+    unsigned nt = std::max(1u, std::thread::hardware_concurrency());
+    if (nt > 64) nt = 64;
+    std::vector<std::thread> th;
+    for (unsigned w = 0; w < nt; ++w) {
+        th.emplace_back([=, &g] {
+            const uint64_t i0 = n * w / nt, i1 = n * (w + 1) / nt;
+            for (uint64_t i = i0; i < i1; ++i) {
+                const uint64_t h = g.key(ti, i);
+                const uint32_t sel = (uint32_t) h & 1023u;
+                uint32_t v;
+                if (sel == 0) v = 0x00000000u;
+                else if (sel == 1) v = 0x80000000u;
+                else if (sel < 4) v = (uint32_t) ((h >> 10) & 0x7fffffu) | (uint32_t) ((h >> 33) & 1u) << 31;   // subnormal
+                else {
+                    const float e = (unit(h) * 16.0f - 8.0f) * (0.5f + unit(h << 24)) * s;
+                    std::memcpy(&v, &e, 4);
+                }
+                out[i] = v;
+            }
+        });
+    }
+    for (auto & t : th) t.join();
+}
+
 }  // namespace
 
 int main(int argc, char ** argv) {
     if (argc < 2) {
         std::fprintf(stderr, "usage: %s OUT [--n-embd N] [--n-head N] [--n-layer N] [--n-mult N] "
-                             "[--n-vocab N] [--ftype 1|2|3] [--seed S] [--vocab FILE]\n", argv[0]);
+                             "[--n-vocab N] [--ftype 0|1|2|3] [--seed S] [--vocab FILE]\n", argv[0]);
         return 2;
     }
     std::string out = argv[1], vocab_path;
@@ -147,7 +176,7 @@ int main(int argc, char ** argv) {
         else if (k == "--vocab") vocab_path = v;
         else { std::fprintf(stderr, "unknown option %s\n", k.c_str()); return 2; }
     }
-    if ((ftype != 1 && ftype != 2 && ftype != 3) || n_embd % 32 || n_head == 0 || n_embd % n_head) {
+    if (ftype > 3 || n_embd % 32 || n_head == 0 || n_embd % n_head) {
         std::fprintf(stderr, "bad hparams\n");
         return 2;
     }
@@ -211,7 +240,11 @@ int main(int argc, char ** argv) {
         th.resize(th.size() + ((32 - (p2 & 31)) & 31), 0);   // llama.cpp:397-400
         std::fwrite(th.data(), 1, th.size(), f);
         pos += th.size();
-        if (is2d && ftype == 1) {
+        if (is2d && ftype == 0) {
+            const uint64_t n = (uint64_t) ne0 * ne1;
+            data.resize(4 * n);
+            fill_f32((uint32_t *) data.data(), n, s, g, ti);
+        } else if (is2d && ftype == 1) {
             const uint64_t n = (uint64_t) ne0 * ne1;
             data.resize(2 * n);
             fill_f16((uint16_t *) data.data(), n, s, g, ti);

@@ -97,6 +97,7 @@ _sig("lvk_mul_mat_q", C.c_int, [C.c_int, u8p, C.c_int, C.c_int, f32p, C.c_int, f
 _sig("lvk_mul_mat_q_norm", C.c_int, [C.c_int, u8p, C.c_int, C.c_int, f32p, f32p, C.c_int, f32p])
 _sig("lvk_mul_mat_q_mfma", C.c_int, [C.c_int, u8p, C.c_int, C.c_int, C.c_void_p, f32p, C.c_int, f32p])
 _sig("lvk_mul_mat_f16", C.c_int, [u16p, C.c_int, C.c_int, C.c_void_p, f32p, C.c_int, f32p, C.c_int])
+_sig("lvk_mul_mat_f32", C.c_int, [f32p, C.c_int, C.c_int, C.c_void_p, f32p, C.c_int, f32p, C.c_int])
 _sig("lvk_attention", C.c_int, [u16p, u16p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p])
 _sig("lvk_attention_prompt", C.c_int, [u16p, u16p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p])
 _sig("lvk_attention_decode", C.c_int, [u16p, u16p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, f32p])
@@ -435,6 +436,22 @@ def mul_mat_f16(w16, x, g=None, kernel=0):
         g = np.ascontiguousarray(g, np.float32)
         gp = g.ctypes.data_as(C.c_void_p)
     _check(lib.lvk_mul_mat_f16(w16.ravel(), m, k, gp, x.ravel(), n, y, kernel), "lvk_mul_mat_f16")
+    return y.reshape(n, m)
+
+
+def mul_mat_f32(w, x, g=None, kernel=0):
+    """f32 weights w [m][k] times f32 rows x [n][k] (lvk_mul_mat_f32); g: optional RMSNorm weight; kernel: 0 as
+    a context chooses, 1 the decode matvec (n == 1), 2 the batched matmul on the f32 matrix cores"""
+    w = np.ascontiguousarray(w, np.float32)
+    m, k = w.shape
+    x = np.ascontiguousarray(x, np.float32).reshape(-1, k)
+    n = x.shape[0]
+    y = np.zeros(n * m, np.float32)
+    gp = None
+    if g is not None:
+        g = np.ascontiguousarray(g, np.float32)
+        gp = g.ctypes.data_as(C.c_void_p)
+    _check(lib.lvk_mul_mat_f32(w.ravel(), m, k, gp, x.ravel(), n, y, kernel), "lvk_mul_mat_f32")
     return y.reshape(n, m)
 
 

@@ -1,6 +1,6 @@
-"""Dev tool: decode and prompt speed of the 7B-shaped f16 synthetic model (32 layers, n_ctx 512,
-lvk-gen-model --ftype 1 --seed 1; a 13.5 GB file under /tmp/lvk_bench).
-usage: f16_speed.py [steps]
+"""Dev tool: decode and prompt speed of the 7B-shaped f16 or f32 synthetic model (32 layers,
+n_ctx 512, lvk-gen-model --ftype 1 | 0 --seed 1; a 13.5 GB / 27 GB file under /tmp/lvk_bench).
+usage: f16_speed.py [steps] [ftype: 1 (default) f16, 0 f32]
 Prints two JSON lines:
   decode: single-stream greedy decode with the window filled by a 512-token prompt, `steps`
           positions spread evenly over 16..511; tok/s, the step's fraction of the 8 TB/s
@@ -26,7 +26,12 @@ PEAK_FLOPS = 157.3e12
 
 def main():
     steps = int(sys.argv[1]) if len(sys.argv) > 1 else 64
-    path = '/tmp/lvk_bench/llama-7b-f16.bin'
+    ftype = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+    if ftype not in (0, 1):
+        sys.exit('ftype: 1 f16, 0 f32')
+    name = '7b-f16' if ftype == 1 else '7b-f32'
+    CFG['ftype'] = ftype
+    path = '/tmp/lvk_bench/llama-%s.bin' % name
     if not os.path.exists(path):
         os.makedirs(os.path.dirname(path), exist_ok=True)
         lvk.gen_model(path, vocab=os.path.join(ROOT, 'tests', 'golden', 'vocab32000.bin'), **CFG)
@@ -69,7 +74,7 @@ def main():
     m.set_profiling(False)
     ks = {k: round(v['ms'] / v['launches'] * 1e3, 2) for k, v in p1.items() if v['launches']}
     gbs = {k: round(v['bytes'] / (v['ms'] * 1e-3) / 1e9, 0) for k, v in p1.items() if v['launches'] and v.get('bytes')}
-    print(json.dumps({'what': 'decode', 'model': '7b-f16 synthetic', 'steps': steps, 'tok_s': round(1 / dt, 1),
+    print(json.dumps({'what': 'decode', 'model': name + ' synthetic', 'steps': steps, 'tok_s': round(1 / dt, 1),
                       'ms_per_token': round(dt * 1e3, 3), 'weight_bytes': wbytes,
                       'roofline_fraction': round(wbytes / dt / PEAK_BW, 3), 'kernels_us': ks, 'gbs': gbs,
                       'load_s': round(load_s, 1)}), flush=True)
@@ -80,7 +85,7 @@ def main():
         m.eval([int(toks[i])], i)
     one_by_one = time.perf_counter() - t0
     m.close()
-    print(json.dumps({'what': 'prompt', 'model': '7b-f16 synthetic', 'n': N_CTX, 'ms': round(best * 1e3, 2),
+    print(json.dumps({'what': 'prompt', 'model': name + ' synthetic', 'n': N_CTX, 'ms': round(best * 1e3, 2),
                       'tok_s': round(N_CTX / best, 1), 'vector_fp32_fraction': round(flop / best / PEAK_FLOPS, 3),
                       'one_token_at_a_time_ms': round(one_by_one * 1e3, 1),
                       'kernels_ms': {k: round(v['ms'], 3) for k, v in pp.items() if v['launches']}}), flush=True)
