@@ -178,6 +178,39 @@ LVK_API int lvk_argmax(const float * x, int n);
  * llama_eval(dst, ., ., n_past = n_tokens, .) exactly as src would.  0 / -1. */
 LVK_API int lvk_kv_copy(struct llama_context * dst, struct llama_context * src, int n_tokens);
 
+/* Batched decode: several sequences per step on one context, one stream of the weights per step.
+ * A context has n_seq KV slots.  Slot 0 is the context's own cache: llama_eval, lvk_eval_greedy /
+ * _sample, lvk_decode_chain, llama_get/set_kv_cache and lvk_kv_copy act on it as ever, and its
+ * token count is llama_get_kv_cache_token_count (an eval of n tokens at n_past leaves n_past + n).
+ * Slots 1..n_seq-1 are further caches of the same layout, zeroed.
+ *
+ * lvk_decode_batch evaluates n rows (tokens[i], seqs[i], pos[i]).  Row i is computed exactly as
+ * llama_eval(ctx', &tokens[i], 1, pos[i], .) computes it on a context whose cache holds sequence
+ * seqs[i]: RoPE at pos[i], K / V appended at pos[i] of slot seqs[i], attention over pos[i] + 1
+ * positions with nothing masked (not the reference's N-token batch, whose columns all run over
+ * n_past + N).  Every logits row is bit-identical to that single-token eval, for Q4_0, Q4_1, f16
+ * and f32 model files.  Rows of one sequence in a call have consecutive ascending positions and
+ * behave like that many single-token evals in order; a sequence's first position in a call is
+ * <= its token count (rewinding is allowed, holes are not), and its count afterwards is its
+ * last position + 1.
+ * Layer-split contexts, stage contexts and contexts with the f32 KV cache (f16_kv = false)
+ * refuse lvk_seq_init: the f32 KV cache has no batched decode. */
+/* allocate slots 1..n_seq-1 (n_seq >= 1; calling again with a larger n_seq grows, smaller is a no-op). 0 / -1;
+ * on failure (out of memory, split / stage context, f16_kv = false) the context is unchanged and usable */
+LVK_API int lvk_seq_init(struct llama_context * ctx, int n_seq);
+LVK_API int lvk_seq_count(struct llama_context * ctx);                 /* slots (1 before lvk_seq_init) */
+LVK_API int lvk_seq_tokens(struct llama_context * ctx, int seq);       /* positions held by a slot, -1 on a bad id */
+/* copy positions [0, n_tokens) of every layer's K and V from slot src to slot dst (device copy), set dst's count;
+ * n_tokens <= src's count */
+LVK_API int lvk_seq_copy(struct llama_context * ctx, int dst, int src, int n_tokens);
+/* n rows (1 <= n <= n_ctx): see above.  logits (optional): [n][n_vocab] floats, row order;
+ * argmax (optional): [n] ints, the reference's first-maximum rule per row, taken on the device.
+ * Every argument is checked before anything is enqueued; 0, or -1 with a message on stderr and the
+ * context and every slot unchanged.  llama_get_logits is NOT refreshed.  The rows count into the
+ * eval timings. */
+LVK_API int lvk_decode_batch(struct llama_context * ctx, const int * tokens, const int * seqs, const int * pos, int n,
+                             float * logits, int * argmax);
+
 /* Pipeline stages (the 65B layer split).  A stage context holds
  * layers [layer_begin, layer_end) of the model file (weights and KV cache); the
  * first stage (layer_begin == 0) also holds the token embeddings, the last one

@@ -195,6 +195,27 @@ bool attention_decode_supported(int n_embd, int n_head, int n_ctx);
 size_t attention_decode_scratch_bytes(int n_head, int n_ctx);
 hipError_t launch_attention_decode(const AttnLaunch & A, void * gran, unsigned epoch, hipStream_t s);
 
+// Batched decode (lvk_decode_batch; attention_rows.hip): n rows, row i a single token of KV slot
+// rows[i].slot at position rows[i].pos, computed as a single-token eval at n_past = pos on that
+// slot's f16 cache.  slots[s]: the base of slot s's K [L][n_ctx][E] and V [L][E][n_ctx];
+// layer_off: the layer's element offset in both (il * n_ctx * E).
+struct SeqRow {
+    int slot, pos;
+};
+struct SeqSlot {
+    uint16_t * kc, * vc;
+};
+// RoPE + KV append of stored Q|K|V rows qkv [n][3E]: q16 [n][E] and, at pos of the row's slot,
+// exactly the K / V stores of launch_rope_kv
+hipError_t launch_rope_kv_rows(const float * qkv, int n, int E, int hd, const float2 * rope, const SeqRow * rows,
+                               const SeqSlot * slots, size_t layer_off, int n_ctx, uint16_t * q16, hipStream_t s);
+// one launch for the n rows (A.n_tokens) of a layer: row i attends over n_kv = pos_i + 1 of its
+// slot, nothing masked; A.kc / A.vc / A.sp / A.scores are not read.  Writes A.out (and A.out_f32)
+// like launch_attention.  Needs head_dim 128, n_ctx % 32 == 0, the f16 cache.
+bool attention_rows_supported(int n_embd, int n_head, int n_ctx);
+hipError_t launch_attention_rows(const AttnLaunch & A, const SeqRow * rows, const SeqSlot * slots, size_t layer_off,
+                                 hipStream_t s);
+
 // one-time weight repack: file-layout rows (ggml blocks) -> quad-sliced image
 // interleave4: src_rows holds two (M/2)-row matrices A then B; the image
 // interleaves them per 4 rows (A0-3, B0-3, A4-7, ...: the fused W1|W3)
@@ -372,6 +393,8 @@ hipError_t launch_rmsnorm_rows(const float * x, const float * g, int K, int n, f
 // greedy argmax over x[0..n) with the reference's first-maximum rule (llama.cpp:1382-1394); *out on the device
 // (out2, optional: a second copy of the token, e.g. host-mapped memory)
 hipError_t launch_argmax(const float * x, int n, int * out, hipStream_t s, int * out2 = nullptr);
+// the same per row of x[rows][n]: out[r] on the device, one launch
+hipError_t launch_argmax_rows(const float * x, int n, int rows, int * out, hipStream_t s);
 // one chained decode step's tail (lvk_decode_chain): the same argmax into chain[CHAIN_HDR + i]
 // (chain[0] = i counts the steps), the logits digest into digest[i] when chain[2] != 0, the next
 // token (forced[i + 1] while i + 1 < chain[1], else the argmax) into the step block (n_past + 1,

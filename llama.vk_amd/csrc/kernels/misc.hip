@@ -350,9 +350,12 @@ __device__ inline ArgBest arg_scan(const float * __restrict__ x, int n) {
     }
     return b;
 }
+// one workgroup per row of x[rows][n] (launch_argmax: one row)
 __global__ __launch_bounds__(1024) void k_argmax_first(const float * __restrict__ x, int n, int * __restrict__ out,
                                                        int * __restrict__ out2) {
     __shared__ ArgBest red[16];
+    x += (size_t) blockIdx.x * n;
+    out += blockIdx.x;
     ArgBest b = arg_scan(x, n);
     for (int off = 32; off > 0; off >>= 1) {
         ArgBest o;
@@ -470,6 +473,12 @@ hipError_t launch_argmax_step(const float * logits, int n, StepParams * sp, int 
 hipError_t launch_argmax(const float * x, int n, int * out, hipStream_t s, int * out2) {
     if (n <= 0) return hipErrorInvalidValue;
     LVK_LAUNCH(k_argmax_first, dim3(1), dim3(1024), 0, s, x, n, out, out2);
+    return hipGetLastError();
+}
+
+hipError_t launch_argmax_rows(const float * x, int n, int rows, int * out, hipStream_t s) {
+    if (n <= 0 || rows <= 0) return hipErrorInvalidValue;
+    LVK_LAUNCH(k_argmax_first, dim3(rows), dim3(1024), 0, s, x, n, out, (int *) nullptr);
     return hipGetLastError();
 }
 }  // namespace lvk

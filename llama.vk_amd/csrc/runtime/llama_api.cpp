@@ -495,8 +495,12 @@ int llama_eval(struct llama_context * ctx, const llama_token * tokens, int n_tok
     lvk::Context & c = ctx->c;
     const int64_t t0 = lvk::now_us();
     try {
-        if (ctx->split) ctx->split->eval(tokens, n_tokens, n_past);
-        else c.eval(tokens, n_tokens, n_past);
+        if (ctx->split) {
+            ctx->split->eval(tokens, n_tokens, n_past);
+            c.kv_n = n_past + n_tokens;
+        } else {
+            c.eval(tokens, n_tokens, n_past);
+        }
     } catch (const lvk::Error & e) {
         fprintf(stderr, "%s: failed to eval: %s\n", __func__, e.msg.c_str());
         return 1;

@@ -75,6 +75,11 @@ Context::~Context() {
     if (samp_h) (void) hipHostFree(samp_h);
     if (sout_h) (void) hipHostFree(sout_h);
     if (greedy_h) (void) hipHostFree(greedy_h);
+    for (SeqKV & s : seq_kv) { (void) hipFree(s.kc); (void) hipFree(s.vc); }
+    if (slots_d) (void) hipFree(slots_d);
+    if (rows_d) (void) hipFree(rows_d);
+    if (amax_d) (void) hipFree(amax_d);
+    if (rows_h) (void) hipHostFree(rows_h);
     for (auto & e : ev_pool) { (void) hipEventDestroy(e.first); (void) hipEventDestroy(e.second); }
     if (sp_h) (void) hipHostFree(sp_h);
     if (tok_h) (void) hipHostFree(tok_h);
@@ -258,15 +263,20 @@ bool Context::use_batched(int n) const {
 //   norm -> W1|W3 (SwiGLU), W2 (+x), then the head.
 // Batches (use_batched) run it as operand image + matmul per matrix, everything else as one
 // matvec launch per matrix with the conversion in its prologue.
-void Context::enqueue_forward(int n, bool last_only, const int * tok_src, int logit_row, bool head, bool embed) {
+//
+// A batched decode step (rows; decode_rows) runs the same sequence.  Its rows sit at a position
+// and on a KV slot each, so the fused QKV epilogues, which place row t at sp->n_past + t of slot
+// 0, are not used: QKV is stored to qkv32, launch_rope_kv_rows appends every row's K / V, and one
+// launch_attention_rows serves all rows.
+void Context::enqueue_forward(int n, bool last_only, const int * tok_src, int logit_row, bool head, bool embed, bool rows) {
     const HParams & hp = model.hp;
     if (!tok_src) tok_src = tok_d;
     float * const logits_out = logits_d + (size_t) logit_row * hp.n_vocab;
     const int E = (int) hp.n_embd, H = (int) hp.n_head, hd = E / H, F = (int) hp.n_ff(), V = (int) hp.n_vocab;
     const int qt = model.qtype;
     const bool batched = use_batched(n);
-    const bool prompt_attn = n > 1 && !kv32 && attention_prompt_supported(E, H, n_ctx);
-    const bool decode_attn = n == 1 && !old_attention && !kv32 && attention_decode_supported(E, H, n_ctx);
+    const bool prompt_attn = !rows && n > 1 && !kv32 && attention_prompt_supported(E, H, n_ctx);
+    const bool decode_attn = !rows && n == 1 && !old_attention && !kv32 && attention_decode_supported(E, H, n_ctx);
     if (decode_attn && !seq_epochs)
         // the decode attention's score granules carry epoch = layer + 1: zero them once per token
         LVK_HIP(hipMemsetAsync(attn_gran, 0, attention_decode_scratch_bytes(H, n_ctx), stream));
@@ -306,9 +316,19 @@ void Context::enqueue_forward(int n, bool last_only, const int * tok_src, int lo
         at.err = err_d;
         at.kv32 = kv32;
         at.seq_epochs = seq_epochs ? 1 : 0;
+        // a batched decode step: RoPE + KV append per row from qkv32, then all rows' attention
+        const size_t layer_off = il * (size_t) n_ctx * E;
+        auto rows_rope_attn = [&] {
+            timed_launch(K_QKV, 0, [&] {
+                return launch_rope_kv_rows(qkv32, n, E, hd, rope, rows_d, slots_d, layer_off, n_ctx, q16, stream);
+            });
+            timed_launch(K_ATTN, 0, [&] { return launch_attention_rows(at, rows_d, slots_d, layer_off, stream); });
+        };
         if (batched) {
             ActImage in = act(K_QKV, x, ly.attn_norm, E);
-            if (!kv32 && mm_rope_fused && mm_epi_supported(qt, EPI_ROPE_KV)) {
+            if (rows) {
+                mm(K_QKV, ly.wqkv, in, qkv32, 3 * E, EPI_STORE);
+            } else if (!kv32 && mm_rope_fused && mm_epi_supported(qt, EPI_ROPE_KV)) {
                 // RoPE + KV append in the matmul's epilogue (the f32 rows never reach memory)
                 const RopeKV rk{rope, sp_d, n_ctx, E, hd, q16, kcl, vcl};
                 mm(K_QKV, ly.wqkv, in, nullptr, 0, EPI_ROPE_KV, &rk);
@@ -321,7 +341,9 @@ void Context::enqueue_forward(int n, bool last_only, const int * tok_src, int lo
             // the Wo input image: written by the prompt attention itself (Q4), else from the
             // attention's f32 rows (f16 weights) or its quantized blocks
             const bool wo_fused = prompt_attn && !attn_f32;
-            if (prompt_attn)
+            if (rows)
+                rows_rope_attn();
+            else if (prompt_attn)
                 timed_launch(K_ATTN, 0, [&] {
                     return launch_attention_prompt(at, (uint16_t *) scores, wo_fused ? img : ActImage{}, stream);
                 });
@@ -347,8 +369,11 @@ void Context::enqueue_forward(int n, bool last_only, const int * tok_src, int lo
         a.w = ly.wqkv; a.x = x; a.g = ly.attn_norm; a.sp = sp_d; a.n_tokens = n;
         a.q16 = q16; a.kc = kcl; a.vc = vcl; a.rope.cs = rope;
         a.n_embd = E; a.head_dim = hd; a.n_ctx = n_ctx; a.kv32 = kv32;
-        timed_launch(K_QKV, qbytes(ly.wqkv), [&] { return launch_matvec_auto(a, PRO_NORM, EPI_QKV, stream); });
-        if (prompt_attn)
+        if (rows) a.y = qkv32;
+        timed_launch(K_QKV, qbytes(ly.wqkv), [&] { return launch_matvec_auto(a, PRO_NORM, rows ? EPI_STORE : EPI_QKV, stream); });
+        if (rows)
+            rows_rope_attn();
+        else if (prompt_attn)
             timed_launch(K_ATTN, 0, [&] { return launch_attention_prompt(at, (uint16_t *) scores, ActImage{}, stream); });
         else if (decode_attn)
             timed_launch(K_ATTN, 0, [&] { return launch_attention_decode(at, attn_gran, (unsigned) il + 1, stream); });
@@ -382,7 +407,7 @@ void Context::enqueue_forward(int n, bool last_only, const int * tok_src, int lo
         o.n_tokens = last_only ? 1 : n;
         timed_launch(K_LMHEAD, qbytes(model.output), [&] { return launch_matvec_auto(o, PRO_NORM, EPI_STORE, stream); });
     }
-    if (want_embedding)
+    if (want_embedding && !rows)
         LVK_HIP(launch_rmsnorm_rows(x + (size_t) (n - 1) * E, model.norm, E, 1, emb_d, stream));
 }
 
@@ -439,6 +464,7 @@ int Context::eval_greedy(int token, int n_past) {
     part.greedy = true;
     begin_eval_safe(&token, 1, n_past, part);
     end_eval(true);
+    kv_n = n_past + 1;
     return *greedy_h;
 }
 
@@ -501,6 +527,7 @@ int Context::decode_chain(const int * tokens, int n_tokens, int n_past, int n_st
         throw;
     }
     end_eval(true);
+    kv_n = n_past + n_steps;
     std::memcpy(out, chain_h, sizeof(int) * (size_t) n_steps);
     if (digests) std::memcpy(digests, digest_h, 8 * (size_t) n_steps);
     return out[n_steps - 1];
@@ -517,6 +544,7 @@ void Context::eval_sample(int token, int n_past) {
     part.sample = true;
     begin_eval_safe(&token, 1, n_past, part);
     end_eval(true);
+    kv_n = n_past + 1;
 }
 
 void Context::fetch_logits() {
@@ -529,6 +557,7 @@ void Context::fetch_logits() {
 void Context::eval(const int * tokens, int n, int n_past) {
     begin_eval_safe(tokens, n, n_past, EvalPart{});
     end_eval(false);
+    kv_n = n_past + n;      // the positions the cache holds: slot 0's count for lvk_decode_batch
 }
 
 // begin_eval for a caller that ends the eval itself: if the enqueue fails part-way, the
@@ -651,6 +680,137 @@ void Context::kv_copy_from(const Context & src, int n_tokens) {
         LVK_HIP(hipStreamSynchronize(stream));
     }
     kv_n = n_tokens;
+}
+
+// KV slots 1..n_seq-1 and, on the first call, the row and slot tables of decode_rows.  Everything
+// new is allocated before anything is committed, so a failure leaves the context as it was.
+void Context::seq_init(int n_seq) {
+    const HParams & hp = model.hp;
+    if (n_seq < 1) throw Error("lvk_seq_init: n_seq must be at least 1");
+    if (kv32) throw Error("lvk_seq_init: batched decode needs the f16 KV cache (f16_kv = true)");
+    if (!model.has_embed || !model.has_head || link) throw Error("lvk_seq_init: not available on a stage context");
+    if (!attention_rows_supported((int) hp.n_embd, (int) hp.n_head, n_ctx))
+        throw Error("lvk_seq_init: batched decode needs head_dim 128");
+    const int have = seq_count();
+    if (n_seq <= have && slots_d) return;
+    const int want = std::max(n_seq, have);
+    const size_t bytes = kv_bytes() / 2, C = (size_t) n_ctx;
+    struct Fresh {      // freed unless committed
+        std::vector<void *> dev;
+        void * host = nullptr;
+        ~Fresh() {
+            for (void * p : dev) (void) hipFree(p);
+            if (host) (void) hipHostFree(host);
+        }
+        void * get(size_t n) {
+            void * p = nullptr;
+            if (hipMalloc(&p, n) != hipSuccess) {
+                (void) hipGetLastError();
+                throw Error("lvk_seq_init: out of device memory");
+            }
+            dev.push_back(p);
+            return p;
+        }
+    } fresh;
+    std::vector<SeqKV> add((size_t) (want - have));
+    for (SeqKV & s : add) {
+        s.kc = (uint16_t *) fresh.get(bytes);
+        s.vc = (uint16_t *) fresh.get(bytes);
+        LVK_HIP(hipMemset(s.kc, 0, bytes));
+        LVK_HIP(hipMemset(s.vc, 0, bytes));
+    }
+    std::vector<SeqSlot> table;
+    table.push_back({kc, vc});
+    for (const SeqKV & s : seq_kv) table.push_back({s.kc, s.vc});
+    for (const SeqKV & s : add) table.push_back({s.kc, s.vc});
+    SeqSlot * table_d = (SeqSlot *) fresh.get(table.size() * sizeof(SeqSlot));
+    SeqRow * rd = rows_d;
+    int * ad = amax_d;
+    if (!rows_d) {
+        rd = (SeqRow *) fresh.get(C * sizeof(SeqRow));
+        ad = (int *) fresh.get(C * sizeof(int));
+        LVK_HIP(hipHostMalloc(&fresh.host, C * sizeof(SeqRow), hipHostMallocDefault));
+    }
+    LVK_HIP(hipStreamSynchronize(stream));      // nothing in flight reads the old table
+    LVK_HIP(hipMemcpy(table_d, table.data(), table.size() * sizeof(SeqSlot), hipMemcpyHostToDevice));
+    // commit
+    if (slots_d) (void) hipFree(slots_d);
+    slots_d = table_d;
+    if (!rows_d) {
+        rows_d = rd;
+        amax_d = ad;
+        rows_h = (SeqRow *) fresh.host;
+        fresh.host = nullptr;
+    }
+    seq_kv.insert(seq_kv.end(), add.begin(), add.end());
+    fresh.dev.clear();
+}
+
+// positions [0, n_tokens) of every layer's K and V from slot src to slot dst, device to device
+// (the copies of kv_copy_from)
+void Context::seq_copy(int dst, int src, int n_tokens) {
+    if (dst < 0 || dst >= seq_count() || src < 0 || src >= seq_count()) throw Error("lvk_seq_copy: sequence id out of range");
+    if (n_tokens < 0 || n_tokens > seq_n(src)) throw Error("lvk_seq_copy: n_tokens exceeds the source sequence");
+    if (dst != src && n_tokens > 0) {
+        const size_t E = model.hp.n_embd, L = model.layers.size(), C = (size_t) n_ctx, n = (size_t) n_tokens, es = kv_elem_bytes();
+        uint16_t * dk = dst == 0 ? kc : seq_kv[(size_t) dst - 1].kc, * dv = dst == 0 ? vc : seq_kv[(size_t) dst - 1].vc;
+        const uint16_t * sk = src == 0 ? kc : seq_kv[(size_t) src - 1].kc, * sv = src == 0 ? vc : seq_kv[(size_t) src - 1].vc;
+        LVK_HIP(hipMemcpy2DAsync(dk, C * E * es, sk, C * E * es, n * E * es, L, hipMemcpyDeviceToDevice, stream));
+        LVK_HIP(hipMemcpy2DAsync(dv, C * es, sv, C * es, n * es, L * E, hipMemcpyDeviceToDevice, stream));
+        LVK_HIP(hipStreamSynchronize(stream));
+    }
+    seq_n(dst) = n_tokens;
+}
+
+// One batched decode step (lvk_decode_batch).  Every argument is checked before anything is
+// enqueued; the slots' counts move only after the step has completed.
+void Context::decode_rows(const int * tokens, const int * seqs, const int * pos, int n, float * logits_out, int * argmax_out) {
+    const HParams & hp = model.hp;
+    const int V = (int) hp.n_vocab;
+    if (!slots_d) seq_init(1);
+    if (!tokens || !seqs || !pos) throw Error("lvk_decode_batch: null argument");
+    if (n < 1 || n > n_ctx_user) throw Error("lvk_decode_batch: the row count must be in 1..n_ctx");
+    // next[s]: the position the next row of slot s must have (-1: no row yet)
+    std::vector<int> next((size_t) seq_count(), -1);
+    for (int i = 0; i < n; ++i) {
+        if (tokens[i] < 0 || tokens[i] >= V) throw Error("lvk_decode_batch: token id out of range");
+        if (seqs[i] < 0 || seqs[i] >= seq_count()) throw Error("lvk_decode_batch: sequence id out of range");
+        if (pos[i] < 0 || pos[i] >= n_ctx_user) throw Error("lvk_decode_batch: position outside n_ctx");
+        int & nx = next[(size_t) seqs[i]];
+        if (nx < 0 && pos[i] > seq_n(seqs[i])) throw Error("lvk_decode_batch: position past the end of its sequence (a hole)");
+        if (nx >= 0 && pos[i] != nx) throw Error("lvk_decode_batch: rows of one sequence must have consecutive ascending positions");
+        nx = pos[i] + 1;
+    }
+    try {
+        if (sp_next > n_ctx) throw Error("llama.vk_amd: too many slices before a sync");
+        StepParams * sh = sp_h + sp_next++;
+        sh->n_past = 0;             // no kernel of this path takes a position from the step block
+        sh->n_tokens = n;
+        sh->pad0 = n == 1 ? tokens[0] : 0;
+        sh->seq = next_seq();
+        std::memcpy(tok_h, tokens, sizeof(int) * (size_t) n);
+        for (int i = 0; i < n; ++i) rows_h[i] = {seqs[i], pos[i]};
+        LVK_HIP(hipMemcpyAsync(sp_d, sh, sizeof(StepParams), hipMemcpyHostToDevice, stream));
+        LVK_HIP(hipMemcpyAsync(tok_d, tok_h, sizeof(int) * (size_t) n, hipMemcpyHostToDevice, stream));
+        LVK_HIP(hipMemcpyAsync(rows_d, rows_h, sizeof(SeqRow) * (size_t) n, hipMemcpyHostToDevice, stream));
+        enqueue_forward(n, false, tok_d, 0, true, true, true);
+        if (argmax_out) {
+            LVK_HIP(launch_argmax_rows(logits_d, V, n, amax_d, stream));
+            LVK_HIP(hipMemcpyAsync(argmax_out, amax_d, sizeof(int) * (size_t) n, hipMemcpyDeviceToHost, stream));
+        }
+        if (logits_out)
+            LVK_HIP(hipMemcpyAsync(logits_out, logits_d, sizeof(float) * (size_t) n * V, hipMemcpyDeviceToHost, stream));
+    } catch (...) {
+        (void) hipStreamSynchronize(stream);
+        sp_next = 1;
+        throw;
+    }
+    // the host logits of llama_get_logits are an earlier eval's: they stay as they are
+    const bool valid = logits_valid;
+    end_eval(true);
+    logits_valid = valid;
+    for (int s = 0; s < seq_count(); ++s)
+        if (next[(size_t) s] >= 0) seq_n(s) = next[(size_t) s];
 }
 
 }  // namespace lvk

@@ -159,6 +159,27 @@ struct Context {
     unsigned seq = 0;            // the last step counter handed to the device
     unsigned next_seq(unsigned k = 1);
 
+    // batched decode (lvk_decode_batch): KV slots beside kc / vc, which are slot 0 with the count
+    // kv_n.  seq_kv[s - 1] is slot s >= 1 in the same layout (f16, zeroed at allocation).
+    struct SeqKV {
+        uint16_t * kc = nullptr;
+        uint16_t * vc = nullptr;
+        int n = 0;               // positions held
+    };
+    std::vector<SeqKV> seq_kv;
+    SeqSlot * slots_d = nullptr; // [seq_count()] base pointers of every slot (nullptr before seq_init)
+    SeqRow * rows_d = nullptr;   // [n_ctx] {slot, pos} of a call's rows
+    SeqRow * rows_h = nullptr;   // pinned staging of them
+    int * amax_d = nullptr;      // [n_ctx] per-row argmax
+    int seq_count() const { return 1 + (int) seq_kv.size(); }
+    int & seq_n(int s) { return s == 0 ? kv_n : seq_kv[(size_t) s - 1].n; }
+    // allocate slots up to n_seq (fewer than now: nothing); on failure nothing has changed
+    void seq_init(int n_seq);
+    void seq_copy(int dst, int src, int n_tokens);
+    // n rows (token, slot, position), each computed as a single-token eval at its position on
+    // its slot; logits [n][V] and argmax [n] are optional host destinations
+    void decode_rows(const int * tokens, const int * seqs, const int * pos, int n, float * logits_out, int * argmax_out);
+
     // host-visible results
     std::vector<float, PinnedAlloc<float>> logits;
     bool logits_valid = false;   // false after lvk_eval_greedy (host logits not refreshed) or a failed eval
@@ -190,8 +211,10 @@ struct Context {
     void end_eval(bool no_host_logits);
     // stage boundary: copy the residual stream x [n][E] to (to_ctx) or from the context
     void x_copy(void * buf, int n, bool to_ctx, bool on_device);
+    // rows: the n tokens are the rows of a batched decode step (rows_d / slots_d) instead of n
+    // consecutive positions of slot 0
     void enqueue_forward(int n, bool last_only, const int * tok_src = nullptr, int logit_row = 0, bool head = true,
-                         bool embed = true);
+                         bool embed = true, bool rows = false);
     bool use_batched(int n) const;
     void build_graph(int kind = 0);      // 0 logits, 1 greedy, 2 sample, 3 chained greedy step
     int eval_greedy(int token, int n_past);

@@ -385,6 +385,46 @@ int lvk_kv_copy(struct llama_context * dst, struct llama_context * src, int n_to
     } catch (const lvk::Error & e) { return fail(__func__, e.msg); }
 }
 
+// ---- batched decode over KV slots (include/lvk_ops.h)
+int lvk_seq_init(struct llama_context * ctx, int n_seq) {
+    try {
+        if (!ctx) throw lvk::Error("null context");
+        if (ctx->split) throw lvk::Error("not available on a layer split");
+        ctx->c.seq_init(n_seq);
+        return 0;
+    } catch (const lvk::Error & e) { return fail(__func__, e.msg); }
+}
+
+int lvk_seq_count(struct llama_context * ctx) { return ctx ? ctx->c.seq_count() : -1; }
+
+int lvk_seq_tokens(struct llama_context * ctx, int seq) {
+    if (!ctx || seq < 0 || seq >= ctx->c.seq_count()) return -1;
+    return ctx->c.seq_n(seq);
+}
+
+int lvk_seq_copy(struct llama_context * ctx, int dst, int src, int n_tokens) {
+    try {
+        if (!ctx) throw lvk::Error("null context");
+        if (ctx->split) throw lvk::Error("not available on a layer split");
+        ctx->c.seq_copy(dst, src, n_tokens);
+        return 0;
+    } catch (const lvk::Error & e) { return fail(__func__, e.msg); }
+}
+
+int lvk_decode_batch(struct llama_context * ctx, const int * tokens, const int * seqs, const int * pos, int n,
+                     float * logits, int * argmax) {
+    try {
+        if (!ctx) throw lvk::Error("null context");
+        if (ctx->split) throw lvk::Error("not available on a layer split");
+        lvk::Context & c = ctx->c;
+        const int64_t t0 = lvk::now_us();
+        c.decode_rows(tokens, seqs, pos, n, logits, argmax);
+        c.t_eval_us += lvk::now_us() - t0;   // n decode evals (llama.cpp:1186-1195)
+        c.n_eval += n;
+        return 0;
+    } catch (const lvk::Error & e) { return fail(__func__, e.msg); }
+}
+
 int lvk_argmax(const float * x, int n) {
     try {
         if (n <= 0) throw lvk::Error("n must be positive");
@@ -433,6 +473,7 @@ int lvk_eval_greedy(struct llama_context * ctx, int token, int n_past) {
     try {
         if (ctx->split) {
             ctx->split->eval(&token, 1, n_past, true);
+            c.kv_n = n_past + 1;
             r = *c.greedy_h;
         } else {
             r = c.eval_greedy(token, n_past);

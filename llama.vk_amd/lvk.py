@@ -119,6 +119,11 @@ _sig("lvk_logits_digest", C.c_uint64, [f32p, C.c_int])
 _sig("lvk_argmax", C.c_int, [f32p, C.c_int])
 _sig("lvk_sample_candidates", C.c_int, [f32p, C.c_int, i32p, C.c_int, C.c_int, C.c_float, C.c_float, f32p, i32p, C.POINTER(C.c_int)])
 _sig("lvk_kv_copy", C.c_int, [C.c_void_p, C.c_void_p, C.c_int])
+_sig("lvk_seq_init", C.c_int, [C.c_void_p, C.c_int])
+_sig("lvk_seq_count", C.c_int, [C.c_void_p])
+_sig("lvk_seq_tokens", C.c_int, [C.c_void_p, C.c_int])
+_sig("lvk_seq_copy", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int])
+_sig("lvk_decode_batch", C.c_int, [C.c_void_p, i32p, i32p, i32p, C.c_int, C.c_void_p, C.c_void_p])
 _sig("lvk_init_stage", C.c_void_p, [C.c_char_p, llama_context_params, C.c_int, C.c_int])
 _sig("lvk_stage_eval", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int])
 _sig("lvk_stage_get_x", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int])
@@ -200,6 +205,41 @@ class Llama:
     def kv_copy_from(self, src, n_tokens):
         """take positions [0, n_tokens) of src's KV cache, device to device (lvk_kv_copy)"""
         _check(lib.lvk_kv_copy(self.ctx, src.ctx, int(n_tokens)), "lvk_kv_copy")
+
+    # ---- batched decode over KV slots (lvk_seq_* / lvk_decode_batch)
+    def seq_init(self, n_seq):
+        """allocate KV slots 1..n_seq-1 beside the context's own cache, slot 0 (lvk_seq_init)"""
+        if lib.lvk_seq_init(self.ctx, int(n_seq)) != 0:
+            raise RuntimeError("lvk_seq_init failed")
+
+    def seq_count(self):
+        return lib.lvk_seq_count(self.ctx)
+
+    def seq_tokens(self, seq):
+        """positions held by a slot (-1 on a bad id)"""
+        return lib.lvk_seq_tokens(self.ctx, int(seq))
+
+    def seq_copy(self, dst, src, n_tokens):
+        """positions [0, n_tokens) of slot src's K and V to slot dst, device to device"""
+        if lib.lvk_seq_copy(self.ctx, int(dst), int(src), int(n_tokens)) != 0:
+            raise RuntimeError("lvk_seq_copy failed")
+
+    def decode_batch(self, tokens, seqs, pos, logits=True, argmax=False):
+        """one step over n rows (token, slot, position), each computed as a single-token eval at
+        its position on its slot (lvk_decode_batch).  Returns (logits [n][n_vocab] float32 or
+        None, argmax int32 [n] or None)."""
+        t = np.ascontiguousarray(tokens, np.int32).reshape(-1)
+        s = np.ascontiguousarray(seqs, np.int32).reshape(-1)
+        p = np.ascontiguousarray(pos, np.int32).reshape(-1)
+        if not (len(t) == len(s) == len(p)):
+            raise ValueError("decode_batch: tokens, seqs and pos differ in length")
+        lg = np.empty((len(t), self.n_vocab), np.float32) if logits else None
+        am = np.empty(len(t), np.int32) if argmax else None
+        r = lib.lvk_decode_batch(self.ctx, t, s, p, len(t), lg.ctypes.data if logits else None,
+                                 am.ctypes.data if argmax else None)
+        if r != 0:
+            raise RuntimeError("lvk_decode_batch failed")
+        return lg, am
 
     def eval_greedy(self, token, n_past):
         """decode one token and pick the next greedily on the device (lvk_eval_greedy);

@@ -1,0 +1,126 @@
+"""Dev tool: aggregate decode rate of a batched decode step (lvk_decode_batch), one row per
+sequence, against the single-sequence llama_eval decode of the same process.
+usage: seq_batch_speed.py [7b|13b|7b-f16 ...] [--steps N] [--out FILE]
+Synthetic models (the bench's seeded files under /tmp/lvk_bench), n_ctx 512.  Slot 0 is filled by
+a 511-token prompt and copied to slots 1..64 at lengths spread evenly over 16..511; a step
+evaluates one row at the end of each of the first S slots, S = 1, 2, 4, ..., 64 (7b) or 16 (the
+others), and is repeated at the same positions (a rewind).  Per S: the median step time over
+`steps` steps after 3 warm-up steps, with the logits rows copied out and with only the device
+argmax; aggregate tok/s = S / step time.  The yardstick is llama_eval (the captured decode graph)
+on slot 0 at the 64 positions.  The per-class device profile is taken at S = 16.  Appends one
+record per model to the JSON file (default profiles/seq_batch_speed.json) and prints it."""
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, 'llama.vk_amd'))
+import numpy as np
+import lvk
+
+CFG = {'7b': ('llama-7b-q4_0.bin', dict(n_embd=4096, n_head=32, n_layer=32, ftype=2, seed=1)),
+       '13b': ('llama-13b-q4_1.bin', dict(n_embd=5120, n_head=40, n_layer=40, ftype=3, seed=2)),
+       '7b-f16': ('llama-7b-f16.bin', dict(n_embd=4096, n_head=32, n_layer=32, ftype=1, seed=1))}
+N_CTX = 512
+N_SLOT = 64
+
+
+def spread(n):
+    """n positions spread evenly over 16..511 (the middle one for n = 1)"""
+    if n == 1:
+        return [(16 + N_CTX - 1) // 2]
+    return [16 + (i * (N_CTX - 1 - 16)) // (n - 1) for i in range(n)]
+
+
+def median_ms(fn, steps, warm=3):
+    for _ in range(warm):
+        fn()
+    ts = []
+    for _ in range(steps):
+        t0 = time.perf_counter()
+        fn()
+        ts.append(time.perf_counter() - t0)
+    return float(np.median(ts)) * 1e3
+
+
+def run(name, steps):
+    fn, cfg = CFG[name]
+    path = os.path.join('/tmp/lvk_bench', fn)
+    if not os.path.exists(path):
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        lvk.gen_model(path, vocab=os.path.join(ROOT, 'tests', 'golden', 'vocab32000.bin'), **cfg)
+    sweep = [1, 2, 4, 8, 16, 32, 64] if name == '7b' else [16]
+    m = lvk.Llama(path, n_ctx=N_CTX)
+    toks = np.array([1] + [100 + (i * 7919) % 31000 for i in range(1, N_CTX - 1)], np.int32)
+    m.eval(toks, 0)
+    m.seq_init(1 + max(sweep))
+    row_tok = [int(100 + (s * 104729) % 31000) for s in range(N_SLOT)]
+
+    # the yardstick: single-sequence llama_eval on slot 0 at the 64 positions
+    pos64 = spread(N_SLOT)
+    for p in pos64[:8]:
+        m.eval([row_tok[0]], p)
+    ts = []
+    for i, p in enumerate(pos64):
+        t0 = time.perf_counter()
+        m.eval([row_tok[i]], p)
+        ts.append(time.perf_counter() - t0)
+    single = {'positions': len(pos64), 'tok_s': round(len(ts) / sum(ts), 1), 'median_ms': round(float(np.median(ts)) * 1e3, 3)}
+    m.eval(toks, 0)          # slot 0 holds the prompt again
+
+    rec = {'model': name + ' synthetic', 'n_ctx': N_CTX, 'steps': steps, 'weight_bytes': m.weight_bytes(),
+           'single_sequence_llama_eval': single, 'batch': []}
+    for S in sweep:
+        pos = spread(S)
+        for s, p in enumerate(pos):
+            m.seq_copy(1 + s, 0, p)
+        seqs = [1 + s for s in range(S)]
+        ms = median_ms(lambda: m.decode_batch(row_tok[:S], seqs, pos), steps)
+        ms_am = median_ms(lambda: m.decode_batch(row_tok[:S], seqs, pos, logits=False, argmax=True), steps)
+        line = {'S': S, 'step_ms': round(ms, 3), 'tok_s': round(S / ms * 1e3, 1),
+                'vs_single': round(S / ms * 1e3 / single['tok_s'], 2),
+                'argmax_only_step_ms': round(ms_am, 3), 'argmax_only_tok_s': round(S / ms_am * 1e3, 1)}
+        if S == 16:
+            m.set_profiling(True)
+            m.reset_profile()
+            for _ in range(4):
+                m.decode_batch(row_tok[:S], seqs, pos)
+            p1 = m.profile()
+            m.set_profiling(False)
+            line['kernels_us_per_launch'] = {k: round(v['ms'] / v['launches'] * 1e3, 2) for k, v in p1.items() if v['launches']}
+            line['class_ms_per_step'] = {k: round(v['ms'] / 4, 3) for k, v in p1.items() if v['launches']}
+        rec['batch'].append(line)
+        print(json.dumps(line), flush=True)
+    if len(sweep) > 1:       # the whole sweep only: a single S says nothing about smaller ones
+        beat = [b['S'] for b in rec['batch'] if b['tok_s'] > single['tok_s']]
+        rec['smallest_S_beating_single'] = min(beat) if beat else None
+    m.close()
+    return rec
+
+
+def main():
+    args = sys.argv[1:]
+    steps, out = 20, os.path.join(ROOT, 'profiles', 'seq_batch_speed.json')
+    names = []
+    while args:
+        a = args.pop(0)
+        if a == '--steps':
+            steps = int(args.pop(0))
+        elif a == '--out':
+            out = args.pop(0)
+        else:
+            names.append(a)
+    recs = json.load(open(out)) if os.path.exists(out) else []
+    for name in names or ['7b']:
+        rec = run(name, steps)
+        recs = [r for r in recs if r['model'] != rec['model']] + [rec]
+        print(json.dumps(rec), flush=True)
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, 'w') as f:
+            json.dump(recs, f, indent=1)
+            f.write('\n')
+
+
+if __name__ == '__main__':
+    main()
