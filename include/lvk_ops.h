@@ -210,6 +210,32 @@ LVK_API int lvk_seq_copy(struct llama_context * ctx, int dst, int src, int n_tok
  * eval timings. */
 LVK_API int lvk_decode_batch(struct llama_context * ctx, const int * tokens, const int * seqs, const int * pos, int n,
                              float * logits, int * argmax);
+/* n_steps batched decode steps in one call.  Row r (0 <= r < n) is sequence seqs[r], starting at
+ * position pos[r].  Step i evaluates, for every row, token t_i[r] at position pos[r] + i on slot
+ * seqs[r], exactly as lvk_decode_batch would with those n rows.  t_0[r] = forced[r];
+ * t_{i+1}[r] = forced[(i + 1) * n + r] while i + 1 < n_forced (1 <= n_forced <= n_steps), else the
+ * argmax (first-maximum rule) of row r's logits of step i.
+ * out_tokens[i * n + r]: that argmax.  out_digests (optional): lvk_logits_digest of that logits row.
+ * logits (optional): the last step's [n][n_vocab].
+ * Nothing crosses PCIe between steps: the steps are replays of one captured graph whose last
+ * kernel picks every row's next token, writes its embedding row and advances the row's position
+ * on the device (with lvk_set_graph(ctx, 0) or the profiler on, the same launches enqueued
+ * eagerly).  Every result is bit-identical to the same rows fed step by step through
+ * lvk_decode_batch.
+ * 1 <= n <= n_ctx; every slot at most once per call (one row per sequence); 0 <= pos[r] <= the
+ * slot's count (rewinding is allowed, holes are not); pos[r] + n_steps <= n_ctx; n_steps >= 1;
+ * every forced token in 0..n_vocab-1.  Everything is checked before anything is enqueued: 0, or -1
+ * with a message on stderr and the context and every slot unchanged.  Afterwards slot seqs[r]
+ * holds pos[r] + n_steps positions.  A context that never called lvk_seq_init has its slot 0;
+ * the contexts that refuse lvk_seq_init refuse this call.  llama_get_logits is NOT refreshed.  The
+ * n * n_steps rows count into the eval timings. */
+LVK_API int lvk_decode_batch_chain(struct llama_context * ctx, const int * forced, int n_forced,
+                                   const int * seqs, const int * pos, int n, int n_steps,
+                                   int * out_tokens, uint64_t * out_digests, float * logits);
+/* one launch of the chain's tail kernel on host logits [n][V]: step index i (same for all rows),
+ * forced [n_forced][n] / n_forced as above.  Writes amax[n], digest[n], next_tok[n].  0 / -1. */
+LVK_API int lvk_rows_step(const float * logits, int n, int V, const int * forced, int n_forced, int step,
+                          int * amax, uint64_t * digest, int * next_tok);
 
 /* Pipeline stages (the 65B layer split).  A stage context holds
  * layers [layer_begin, layer_end) of the model file (weights and KV cache); the

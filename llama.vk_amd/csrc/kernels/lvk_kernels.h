@@ -403,6 +403,15 @@ constexpr int CHAIN_HDR = 4;
 hipError_t launch_argmax_step(const float * logits, int n, StepParams * sp, int * chain, const int * forced,
                               unsigned long long * digest, const void * emb, int emb_type, int n_embd, float * x,
                               hipStream_t s);
+// one chained batched decode step's tail (lvk_decode_batch_chain): launch_argmax_step per row of
+// logits [n][n_vocab], one workgroup each.  Row r's step index is i = rows[r].pos - pos0[r]; its
+// argmax goes to out_tok[i * n + r], the logits digest to digest[i * n + r] when ctl[1] != 0, the
+// next token (forced[(i + 1) * n + r] while i + 1 < ctl[0], else the argmax) to next_tok[r]
+// (optional) and, with emb, its embedding row to x[r][0..n_embd); rows[r].pos advances by one.
+// No workgroup reads a word another one writes.
+hipError_t launch_rows_step(const float * logits, int n_vocab, int n, SeqRow * rows, const int * pos0, const int * ctl,
+                            const int * forced, int * out_tok, unsigned long long * digest, int * next_tok,
+                            const void * emb, int emb_type, int n_embd, float * x, hipStream_t s);
 
 // ---------------------------------------------------------------------------
 // ggml graph operators (graph_ops.hip; include/ggml.h via runtime/ggml_graph.cpp): one

@@ -10,13 +10,9 @@ thread_local LaunchEvents g_launch_events;
 
 namespace {
 
-// get_rows + dequantize_row_q4_0/q4_1 AVX2 (ggml.c:6868-6895, 968-1000, 1086-1115)
-__global__ void k_embed(const uint8_t * __restrict__ emb, int type, int E, const int * __restrict__ tokens,
-                        float * __restrict__ x) {
-    const int t = blockIdx.y;
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= E) return;
-    const size_t tok = (size_t) tokens[t];
+// element e of token tok's embedding row: get_rows + dequantize_row_q4_0/q4_1 AVX2
+// (ggml.c:6868-6895, 968-1000, 1086-1115); every kernel that writes an embedding row takes it here
+__device__ __forceinline__ float embed_value(const uint8_t * __restrict__ emb, int type, int E, size_t tok, int e) {
     float v;
     if (type == Q4_0) {
         const uint8_t * b = emb + tok * (size_t) (E / 32) * 20 + (size_t) (e / 32) * 20;
@@ -36,7 +32,15 @@ __global__ void k_embed(const uint8_t * __restrict__ emb, int type, int E, const
     } else {                  // f32
         v = ((const float *) emb)[tok * E + e];
     }
-    x[(size_t) t * E + e] = v;
+    return v;
+}
+
+__global__ void k_embed(const uint8_t * __restrict__ emb, int type, int E, const int * __restrict__ tokens,
+                        float * __restrict__ x) {
+    const int t = blockIdx.y;
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    x[(size_t) t * E + e] = embed_value(emb, type, E, (size_t) tokens[t], e);
 }
 
 // Q4_0 file rows -> octet image (matvec_q4.hip).  One thread per
@@ -350,12 +354,9 @@ __device__ inline ArgBest arg_scan(const float * __restrict__ x, int n) {
     }
     return b;
 }
-// one workgroup per row of x[rows][n] (launch_argmax: one row)
-__global__ __launch_bounds__(1024) void k_argmax_first(const float * __restrict__ x, int n, int * __restrict__ out,
-                                                       int * __restrict__ out2) {
-    __shared__ ArgBest red[16];
-    x += (size_t) blockIdx.x * n;
-    out += blockIdx.x;
+// the 1024-thread workgroup's scan of x[0..n): every wave's best into red[16] (a barrier later,
+// arg_first reads them)
+__device__ inline void arg_scan_waves(const float * __restrict__ x, int n, ArgBest * red) {
     ArgBest b = arg_scan(x, n);
     for (int off = 32; off > 0; off >>= 1) {
         ArgBest o;
@@ -364,12 +365,24 @@ __global__ __launch_bounds__(1024) void k_argmax_first(const float * __restrict_
         b = arg_pick(b, o);
     }
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = b;
+}
+// one thread, after the barrier: the token of the rule above
+__device__ inline int arg_first(const ArgBest * red, const float * __restrict__ x, int n) {
+    ArgBest r = red[0];
+    for (int w = 1; w < 16; ++w) r = arg_pick(r, red[w]);
+    const bool nan0 = n > 0 && !(x[0] == x[0]);
+    return (nan0 || r.i == INT_MAX) ? 0 : r.i;
+}
+// one workgroup per row of x[rows][n] (launch_argmax: one row)
+__global__ __launch_bounds__(1024) void k_argmax_first(const float * __restrict__ x, int n, int * __restrict__ out,
+                                                       int * __restrict__ out2) {
+    __shared__ ArgBest red[16];
+    x += (size_t) blockIdx.x * n;
+    out += blockIdx.x;
+    arg_scan_waves(x, n, red);
     __syncthreads();
     if (threadIdx.x == 0) {
-        ArgBest r = red[0];
-        for (int w = 1; w < 16; ++w) r = arg_pick(r, red[w]);
-        const bool nan0 = n > 0 && !(x[0] == x[0]);
-        const int tok = (nan0 || r.i == INT_MAX) ? 0 : r.i;
+        const int tok = arg_first(red, x, n);
         out[0] = tok;
         if (out2) out2[0] = tok;     // e.g. host-mapped memory: visible after the stream completes
     }
@@ -387,6 +400,21 @@ __device__ __forceinline__ unsigned long long digest_mix(unsigned long long z) {
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     return z ^ (z >> 31);
 }
+// the 1024-thread workgroup's digest of logits[0..n): the sum over the row of
+// mix(index << 32 | bits) -- wrap-around adds, any order gives the same -- per wave into dred[16]
+__device__ inline void digest_scan_waves(const float * __restrict__ logits, int n, unsigned long long * dred) {
+    unsigned long long dg = 0;
+    for (int k = threadIdx.x; k < n; k += 1024)
+        dg += digest_mix(((unsigned long long) k << 32) | __float_as_uint(logits[k]));
+    for (int off = 32; off > 0; off >>= 1) dg += __shfl_xor(dg, off, 64);
+    if ((threadIdx.x & 63) == 0) dred[threadIdx.x >> 6] = dg;
+}
+// one thread, after the barrier
+__device__ inline unsigned long long digest_total(const unsigned long long * dred) {
+    unsigned long long dg = 0;
+    for (int w = 0; w < 16; ++w) dg += dred[w];
+    return dg;
+}
 __global__ __launch_bounds__(1024) void k_argmax_step(const float * __restrict__ logits, int n, StepParams * sp,
                                                       int * chain, const int * __restrict__ forced,
                                                       unsigned long long * __restrict__ digest,
@@ -397,37 +425,16 @@ __global__ __launch_bounds__(1024) void k_argmax_step(const float * __restrict__
     __shared__ int s_tok;
     const int i = chain[0], n_forced = chain[1];
     const bool want_digest = chain[2] != 0;
-    ArgBest b = arg_scan(logits, n);
-    for (int off = 32; off > 0; off >>= 1) {
-        ArgBest o;
-        o.v = __shfl_xor(b.v, off, 64);
-        o.i = __shfl_xor(b.i, off, 64);
-        b = arg_pick(b, o);
-    }
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = b;
-    if (want_digest) {
-        // sum over the row of mix(index << 32 | bits): wrap-around adds, any order gives the same
-        unsigned long long dg = 0;
-        for (int k = threadIdx.x; k < n; k += 1024)
-            dg += digest_mix(((unsigned long long) k << 32) | __float_as_uint(logits[k]));
-        for (int off = 32; off > 0; off >>= 1) dg += __shfl_xor(dg, off, 64);
-        if ((threadIdx.x & 63) == 0) dred[threadIdx.x >> 6] = dg;
-    }
+    arg_scan_waves(logits, n, red);
+    if (want_digest) digest_scan_waves(logits, n, dred);
     __syncthreads();
     if (threadIdx.x == 0) {
-        ArgBest r = red[0];
-        for (int w = 1; w < 16; ++w) r = arg_pick(r, red[w]);
-        const bool nan0 = n > 0 && !(logits[0] == logits[0]);
-        const int amax = (nan0 || r.i == INT_MAX) ? 0 : r.i;
+        const int amax = arg_first(red, logits, n);
         const int tok = i + 1 < n_forced ? forced[i + 1] : amax;
         s_tok = tok;
         chain[CHAIN_HDR + i] = amax;
         chain[0] = i + 1;
-        if (want_digest) {
-            unsigned long long dg = 0;
-            for (int w = 0; w < 16; ++w) dg += dred[w];
-            digest[i] = dg;
-        }
+        if (want_digest) digest[i] = digest_total(dred);
         StepParams st = *sp;
         st.n_past += 1;
         st.pad0 = tok;
@@ -436,30 +443,60 @@ __global__ __launch_bounds__(1024) void k_argmax_step(const float * __restrict__
     }
     __syncthreads();
     const size_t tok = (size_t) s_tok;
-    for (int e = threadIdx.x; e < E; e += 1024) {
-        float v;
-        if (type == Q4_0) {
-            const uint8_t * blk = emb + tok * (size_t) (E / 32) * 20 + (size_t) (e / 32) * 20;
-            const float d = *(const float *) blk;
-            const uint8_t byte = blk[4 + (e % 32) / 2];
-            const int qv = (e & 1) ? (byte >> 4) : (byte & 15);
-            v = (float) (qv - 8) * d;
-        } else if (type == Q4_1) {
-            const uint8_t * blk = emb + tok * (size_t) (E / 32) * 24 + (size_t) (e / 32) * 24;
-            const float d = *(const float *) blk, m = *(const float *) (blk + 4);
-            const uint8_t byte = blk[8 + (e % 32) / 2];
-            const int qv = (e & 1) ? (byte >> 4) : (byte & 15);
-            const float a = (float) qv * d;
-            v = a + m;
-        } else if (type == 1) {
-            v = f16_to_f32(((const uint16_t *) emb)[tok * E + e]);
-        } else {
-            v = ((const float *) emb)[tok * E + e];
-        }
-        x[e] = v;
+    for (int e = threadIdx.x; e < E; e += 1024) x[e] = embed_value(emb, type, E, tok, e);
+}
+
+// the last kernel of a chained batched decode step (lvk_decode_batch_chain): k_argmax_step per
+// row, one workgroup per row r of logits[n][V].  Step index i = rows[r].pos - pos0[r] (pos0: the
+// row's position at the call's start), so a workgroup reads and writes only its own row's words:
+// the argmax goes to out_tok[i * n + r], the digest to digest[i * n + r] when ctl[1] != 0, the
+// next token -- forced[(i + 1) * n + r] while i + 1 < ctl[0], else the argmax -- to next_tok[r]
+// (optional) and, as its embedding row, to x[r] (emb == nullptr: not written); rows[r].pos
+// advances by one: everything the next replay of the step's launches reads
+__global__ __launch_bounds__(1024) void k_rows_step(const float * __restrict__ logits, int V, SeqRow * rows,
+                                                    const int * __restrict__ pos0, const int * __restrict__ ctl,
+                                                    const int * __restrict__ forced, int * __restrict__ out_tok,
+                                                    unsigned long long * __restrict__ digest,
+                                                    int * __restrict__ next_tok, const uint8_t * __restrict__ emb,
+                                                    int type, int E, float * __restrict__ x) {
+    __shared__ ArgBest red[16];
+    __shared__ unsigned long long dred[16];
+    __shared__ int s_tok;
+    const int r = blockIdx.x, n = gridDim.x;
+    const int n_forced = ctl[0];
+    const bool want_digest = ctl[1] != 0;
+    logits += (size_t) r * V;
+    arg_scan_waves(logits, V, red);
+    if (want_digest) digest_scan_waves(logits, V, dred);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const SeqRow rw = rows[r];
+        const int i = rw.pos - pos0[r];
+        const int amax = arg_first(red, logits, V);
+        const int tok = i + 1 < n_forced ? forced[(size_t) (i + 1) * n + r] : amax;
+        s_tok = tok;
+        out_tok[(size_t) i * n + r] = amax;
+        if (want_digest) digest[(size_t) i * n + r] = digest_total(dred);
+        if (next_tok) next_tok[r] = tok;
+        rows[r].pos = rw.pos + 1;
     }
+    __syncthreads();
+    if (!emb) return;
+    const size_t tok = (size_t) s_tok;
+    x += (size_t) r * E;
+    for (int e = threadIdx.x; e < E; e += 1024) x[e] = embed_value(emb, type, E, tok, e);
 }
 }  // namespace
+
+hipError_t launch_rows_step(const float * logits, int n_vocab, int n, SeqRow * rows, const int * pos0, const int * ctl,
+                            const int * forced, int * out_tok, unsigned long long * digest, int * next_tok,
+                            const void * emb, int emb_type, int n_embd, float * x, hipStream_t s) {
+    if (n <= 0 || n_vocab <= 0 || !rows || !pos0 || !ctl || !forced || !out_tok || !digest) return hipErrorInvalidValue;
+    if (emb && (n_embd <= 0 || n_embd % 32 || !x)) return hipErrorInvalidValue;
+    LVK_LAUNCH(k_rows_step, dim3(n), dim3(1024), 0, s, logits, n_vocab, rows, pos0, ctl, forced, out_tok, digest, next_tok,
+               (const uint8_t *) emb, emb_type, n_embd, x);
+    return hipGetLastError();
+}
 
 hipError_t launch_argmax_step(const float * logits, int n, StepParams * sp, int * chain, const int * forced,
                               unsigned long long * digest, const void * emb, int emb_type, int n_embd, float * x,

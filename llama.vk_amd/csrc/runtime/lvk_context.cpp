@@ -68,6 +68,11 @@ Context::~Context() {
     if (graph_sample) (void) hipGraphDestroy(graph_sample);
     if (graph_chain_exec) (void) hipGraphExecDestroy(graph_chain_exec);
     if (graph_chain) (void) hipGraphDestroy(graph_chain);
+    drop_rows_graph();
+    for (void * p : {(void *) rc_tok_d, (void *) rc_dig_d, (void *) rc_forced_d, (void *) rc_ctl_d})
+        if (p) (void) hipFree(p);
+    for (void * p : {(void *) rc_tok_h, (void *) rc_dig_h, (void *) rc_forced_h, (void *) rc_ctl_h})
+        if (p) (void) hipHostFree(p);
     if (chain_h) (void) hipHostFree(chain_h);
     if (chain_ctl_h) (void) hipHostFree(chain_ctl_h);
     if (forced_h) (void) hipHostFree(forced_h);
@@ -734,6 +739,7 @@ void Context::seq_init(int n_seq) {
     LVK_HIP(hipStreamSynchronize(stream));      // nothing in flight reads the old table
     LVK_HIP(hipMemcpy(table_d, table.data(), table.size() * sizeof(SeqSlot), hipMemcpyHostToDevice));
     // commit
+    drop_rows_graph();      // its launches hold the old slot table
     if (slots_d) (void) hipFree(slots_d);
     slots_d = table_d;
     if (!rows_d) {
@@ -811,6 +817,164 @@ void Context::decode_rows(const int * tokens, const int * seqs, const int * pos,
     logits_valid = valid;
     for (int s = 0; s < seq_count(); ++s)
         if (next[(size_t) s] >= 0) seq_n(s) = next[(size_t) s];
+}
+
+void Context::drop_rows_graph() {
+    if (graph_rows_exec) (void) hipGraphExecDestroy(graph_rows_exec);
+    if (graph_rows) (void) hipGraphDestroy(graph_rows);
+    graph_rows_exec = nullptr;
+    graph_rows = nullptr;
+    graph_rows_n = 0;
+}
+
+// room for `entries` = n_steps * n tokens, digests and forced tokens of a chained batched decode,
+// on the device and page-locked on the host, and on the first call the control block.  Everything
+// new is allocated before anything is committed (as seq_init); the step graph holds the old
+// addresses, so it goes with them.
+void Context::rows_chain_reserve(size_t entries) {
+    if (entries <= rc_cap && rc_ctl_d) return;
+    const size_t cap = std::max(std::max(entries, rc_cap), (size_t) n_ctx);
+    struct Fresh {      // freed unless committed
+        std::vector<void *> dev, host;
+        ~Fresh() {
+            for (void * p : dev) (void) hipFree(p);
+            for (void * p : host) (void) hipHostFree(p);
+        }
+        void * get(size_t n, bool pinned) {
+            void * p = nullptr;
+            const hipError_t e = pinned ? hipHostMalloc(&p, n, hipHostMallocDefault) : hipMalloc(&p, n);
+            if (e != hipSuccess) {
+                (void) hipGetLastError();
+                throw Error("lvk_decode_batch_chain: out of memory for the step outputs");
+            }
+            (pinned ? host : dev).push_back(p);
+            return p;
+        }
+    } fresh;
+    int * tok_dn = (int *) fresh.get(cap * sizeof(int), false), * tok_hn = (int *) fresh.get(cap * sizeof(int), true);
+    auto * dig_dn = (unsigned long long *) fresh.get(cap * 8, false), * dig_hn = (unsigned long long *) fresh.get(cap * 8, true);
+    int * for_dn = (int *) fresh.get(cap * sizeof(int), false), * for_hn = (int *) fresh.get(cap * sizeof(int), true);
+    int * ctl_dn = rc_ctl_d, * ctl_hn = rc_ctl_h;
+    if (!rc_ctl_d) {
+        ctl_dn = (int *) fresh.get((2 + (size_t) n_ctx) * sizeof(int), false);
+        ctl_hn = (int *) fresh.get((2 + (size_t) n_ctx) * sizeof(int), true);
+    }
+    LVK_HIP(hipStreamSynchronize(stream));      // nothing in flight uses the old buffers
+    // commit
+    drop_rows_graph();
+    for (void * p : {(void *) rc_tok_d, (void *) rc_dig_d, (void *) rc_forced_d})
+        if (p) (void) hipFree(p);
+    for (void * p : {(void *) rc_tok_h, (void *) rc_dig_h, (void *) rc_forced_h})
+        if (p) (void) hipHostFree(p);
+    rc_tok_d = tok_dn; rc_tok_h = tok_hn;
+    rc_dig_d = dig_dn; rc_dig_h = dig_hn;
+    rc_forced_d = for_dn; rc_forced_h = for_hn;
+    rc_ctl_d = ctl_dn; rc_ctl_h = ctl_hn;
+    rc_cap = cap;
+    fresh.dev.clear();
+    fresh.host.clear();
+}
+
+// n_steps batched decode steps in one call (lvk_decode_batch_chain): step i evaluates, for every
+// row r, token t_i[r] at pos[r] + i on slot seqs[r], as decode_rows would with those n rows;
+// t_0[r] = forced[r], t_{i+1}[r] = forced[(i + 1) * n + r] while i + 1 < n_forced, else the argmax
+// of row r's logits of step i.  The host sets the rows, the forced table and the first embedding
+// rows up once; each step is the rows' forward pass followed by k_rows_step, which leaves x and
+// rows_d as the next step reads them.  The rows path of enqueue_forward takes positions and slots
+// from rows_d / slots_d alone (sp_d is read only by the fused QKV epilogues, which a rows step
+// does not run), so the step block needs no advancing on the device.  The steps are replays of
+// one captured graph, or the same launches enqueued eagerly when the graph is off or the
+// profiler is on.  Every argument is checked before anything is enqueued; the slots' counts move
+// only after the last step has completed.
+void Context::decode_rows_chain(const int * forced, int n_forced, const int * seqs, const int * pos, int n, int n_steps,
+                                int * out_tokens, unsigned long long * out_digests, float * logits_out) {
+    const HParams & hp = model.hp;
+    const int V = (int) hp.n_vocab, E = (int) hp.n_embd;
+    if (!slots_d) seq_init(1);
+    if (!forced || !seqs || !pos || !out_tokens) throw Error("lvk_decode_batch_chain: null argument");
+    if (n < 1 || n > n_ctx_user) throw Error("lvk_decode_batch_chain: the row count must be in 1..n_ctx");
+    if (n_steps < 1 || n_steps > n_ctx_user) throw Error("lvk_decode_batch_chain: n_steps must be in 1..n_ctx");
+    if (n_forced < 1 || n_forced > n_steps) throw Error("lvk_decode_batch_chain: n_forced must be in 1..n_steps");
+    std::vector<char> named((size_t) seq_count(), 0);
+    for (int r = 0; r < n; ++r) {
+        if (seqs[r] < 0 || seqs[r] >= seq_count()) throw Error("lvk_decode_batch_chain: sequence id out of range");
+        if (named[(size_t) seqs[r]]) throw Error("lvk_decode_batch_chain: a sequence may have one row only");
+        named[(size_t) seqs[r]] = 1;
+        if (pos[r] < 0 || pos[r] > seq_n(seqs[r]))
+            throw Error("lvk_decode_batch_chain: position past the end of its sequence (a hole)");
+        if (pos[r] > n_ctx_user - n_steps) throw Error("lvk_decode_batch_chain: pos + n_steps exceeds n_ctx");
+    }
+    const size_t nf = (size_t) n_forced * n, total = (size_t) n_steps * n;
+    for (size_t k = 0; k < nf; ++k)
+        if (forced[k] < 0 || forced[k] >= V) throw Error("lvk_decode_batch_chain: token id out of range");
+    rows_chain_reserve(total);
+    auto step = [&] {
+        enqueue_forward(n, false, tok_d, 0, true, /*embed=*/false, /*rows=*/true);
+        LVK_HIP(launch_rows_step(logits_d, V, n, rows_d, rc_ctl_d + 2, rc_ctl_d, rc_forced_d, rc_tok_d, rc_dig_d, nullptr,
+                                 model.tok_emb, model.emb_type, E, x, stream));
+    };
+    try {
+        if (sp_next > n_ctx) throw Error("llama.vk_amd: too many slices before a sync");
+        StepParams * sh = sp_h + sp_next++;
+        sh->n_past = 0;             // no kernel of this path takes a position from the step block
+        sh->n_tokens = n;
+        sh->pad0 = 0;
+        sh->seq = next_seq((unsigned) n_steps);
+        rc_ctl_h[0] = n_forced;
+        rc_ctl_h[1] = out_digests ? 1 : 0;
+        for (int r = 0; r < n; ++r) {
+            rows_h[r] = {seqs[r], pos[r]};
+            rc_ctl_h[2 + r] = pos[r];
+        }
+        std::memcpy(rc_forced_h, forced, sizeof(int) * nf);
+        LVK_HIP(hipMemcpyAsync(sp_d, sh, sizeof(StepParams), hipMemcpyHostToDevice, stream));
+        LVK_HIP(hipMemcpyAsync(rows_d, rows_h, sizeof(SeqRow) * (size_t) n, hipMemcpyHostToDevice, stream));
+        LVK_HIP(hipMemcpyAsync(rc_ctl_d, rc_ctl_h, sizeof(int) * (2 + (size_t) n), hipMemcpyHostToDevice, stream));
+        LVK_HIP(hipMemcpyAsync(rc_forced_d, rc_forced_h, sizeof(int) * nf, hipMemcpyHostToDevice, stream));
+        LVK_HIP(launch_embed(model.tok_emb, model.emb_type, E, rc_forced_d, n, x, stream));
+        if (use_graph && !profiling) {
+            // the row count (and the matmul path it selects) is baked into the graph's launches
+            if (graph_rows_exec && (graph_rows_n != n || graph_rows_exact != prompt_exact)) drop_rows_graph();
+            if (!graph_rows_exec) {
+                LVK_HIP(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
+                try {
+                    step();
+                } catch (...) {
+                    hipGraph_t g = nullptr;
+                    (void) hipStreamEndCapture(stream, &g);
+                    if (g) (void) hipGraphDestroy(g);
+                    throw;
+                }
+                LVK_HIP(hipStreamEndCapture(stream, &graph_rows));
+                const hipError_t e = hipGraphInstantiate(&graph_rows_exec, graph_rows, nullptr, nullptr, 0);
+                if (e != hipSuccess) {
+                    graph_rows_exec = nullptr;
+                    drop_rows_graph();
+                    LVK_HIP(e);
+                }
+                graph_rows_n = n;
+                graph_rows_exact = prompt_exact;
+            }
+            for (int i = 0; i < n_steps; ++i) LVK_HIP(hipGraphLaunch(graph_rows_exec, stream));
+        } else {
+            for (int i = 0; i < n_steps; ++i) step();
+        }
+        LVK_HIP(hipMemcpyAsync(rc_tok_h, rc_tok_d, sizeof(int) * total, hipMemcpyDeviceToHost, stream));
+        if (out_digests) LVK_HIP(hipMemcpyAsync(rc_dig_h, rc_dig_d, 8 * total, hipMemcpyDeviceToHost, stream));
+        if (logits_out)
+            LVK_HIP(hipMemcpyAsync(logits_out, logits_d, sizeof(float) * (size_t) n * V, hipMemcpyDeviceToHost, stream));
+    } catch (...) {
+        (void) hipStreamSynchronize(stream);
+        sp_next = 1;
+        throw;
+    }
+    // the host logits of llama_get_logits are an earlier eval's: they stay as they are
+    const bool valid = logits_valid;
+    end_eval(true);
+    logits_valid = valid;
+    std::memcpy(out_tokens, rc_tok_h, sizeof(int) * total);
+    if (out_digests) std::memcpy(out_digests, rc_dig_h, 8 * total);
+    for (int r = 0; r < n; ++r) seq_n(seqs[r]) = pos[r] + n_steps;
 }
 
 }  // namespace lvk

@@ -179,6 +179,11 @@ struct Context {
     // n rows (token, slot, position), each computed as a single-token eval at its position on
     // its slot; logits [n][V] and argmax [n] are optional host destinations
     void decode_rows(const int * tokens, const int * seqs, const int * pos, int n, float * logits_out, int * argmax_out);
+    // n_steps such steps of n rows, one per slot, in one call (state: the end of this struct)
+    void decode_rows_chain(const int * forced, int n_forced, const int * seqs, const int * pos, int n, int n_steps,
+                           int * out_tokens, unsigned long long * out_digests, float * logits_out);
+    void rows_chain_reserve(size_t entries);
+    void drop_rows_graph();
 
     // host-visible results
     std::vector<float, PinnedAlloc<float>> logits;
@@ -226,6 +231,21 @@ struct Context {
     void collect_profile();
     // after a stream sync: throw if a kernel raised the error word (and clear it)
     void check_device_error();
+
+    // chained batched decode (lvk_decode_batch_chain): one graph per step of n rows that reads
+    // nothing from the host -- the rows' forward pass, then k_rows_step, which picks every row's
+    // next token, writes its embedding row and advances rows_d -- replayed n_steps times per call
+    hipGraph_t graph_rows = nullptr;
+    hipGraphExec_t graph_rows_exec = nullptr;
+    int graph_rows_n = 0;            // the row count baked into the graph's launches
+    bool graph_rows_exact = false;   // prompt_exact at capture (it selects the matmul path)
+    // per call: [n_steps][n] argmax tokens and digests, [n_forced][n] forced tokens (rc_cap
+    // entries each, grown on demand), the rows' start positions and {n_forced, digest flag}
+    size_t rc_cap = 0;
+    int * rc_tok_d = nullptr, * rc_tok_h = nullptr;
+    unsigned long long * rc_dig_d = nullptr, * rc_dig_h = nullptr;
+    int * rc_forced_d = nullptr, * rc_forced_h = nullptr;
+    int * rc_ctl_d = nullptr, * rc_ctl_h = nullptr;       // [2 + n_ctx]: the two control words, then the start positions
 };
 
 int64_t now_us();

@@ -425,6 +425,49 @@ int lvk_decode_batch(struct llama_context * ctx, const int * tokens, const int *
     } catch (const lvk::Error & e) { return fail(__func__, e.msg); }
 }
 
+int lvk_decode_batch_chain(struct llama_context * ctx, const int * forced, int n_forced, const int * seqs, const int * pos,
+                           int n, int n_steps, int * out_tokens, uint64_t * out_digests, float * logits) {
+    try {
+        if (!ctx) throw lvk::Error("null context");
+        if (ctx->split) throw lvk::Error("not available on a layer split");
+        lvk::Context & c = ctx->c;
+        const int64_t t0 = lvk::now_us();
+        c.decode_rows_chain(forced, n_forced, seqs, pos, n, n_steps, out_tokens, (unsigned long long *) out_digests, logits);
+        c.t_eval_us += lvk::now_us() - t0;   // n * n_steps decode evals (llama.cpp:1186-1195)
+        c.n_eval += n * n_steps;
+        return 0;
+    } catch (const lvk::Error & e) { return fail(__func__, e.msg); }
+}
+
+int lvk_rows_step(const float * logits, int n, int V, const int * forced, int n_forced, int step, int * amax,
+                  uint64_t * digest, int * next_tok) {
+    try {
+        // the kernel indexes its outputs by step: (step + 1) * n entries, the last n are this step's
+        if (!logits || !amax || !digest || !next_tok || n <= 0 || V <= 0 || step < 0 || n_forced < 0 ||
+            (n_forced > 0 && !forced) || (size_t) n * ((size_t) step + 1) > ((size_t) 1 << 24) ||
+            (size_t) n * (size_t) n_forced > ((size_t) 1 << 24))
+            throw lvk::Error("arguments out of range");
+        Dev dv;
+        const size_t total = (size_t) n * ((size_t) step + 1), off = (size_t) n * (size_t) step;
+        float * xd = dv.up(logits, (size_t) n * V);
+        std::vector<lvk::SeqRow> rows((size_t) n, lvk::SeqRow{0, step});
+        std::vector<int> ctl(2 + (size_t) n, 0);     // {n_forced, digest flag}, then the start positions (0)
+        ctl[0] = n_forced;
+        ctl[1] = 1;
+        lvk::SeqRow * rd = dv.up(rows.data(), rows.size());
+        int * cd = dv.up(ctl.data(), ctl.size());
+        int * fd = n_forced > 0 ? dv.up(forced, (size_t) n * n_forced) : (int *) dv.get(4);
+        int * od = (int *) dv.get(total * sizeof(int));
+        auto * dd = (unsigned long long *) dv.get(total * 8);
+        int * nd = (int *) dv.get((size_t) n * sizeof(int));
+        LVK_HIP(lvk::launch_rows_step(xd, V, n, rd, cd + 2, cd, fd, od, dd, nd, nullptr, 0, 0, nullptr, nullptr));
+        LVK_HIP(hipMemcpy(amax, od + off, sizeof(int) * (size_t) n, hipMemcpyDeviceToHost));
+        LVK_HIP(hipMemcpy(digest, dd + off, 8 * (size_t) n, hipMemcpyDeviceToHost));
+        LVK_HIP(hipMemcpy(next_tok, nd, sizeof(int) * (size_t) n, hipMemcpyDeviceToHost));
+        return 0;
+    } catch (const lvk::Error & e) { return fail(__func__, e.msg); }
+}
+
 int lvk_argmax(const float * x, int n) {
     try {
         if (n <= 0) throw lvk::Error("n must be positive");

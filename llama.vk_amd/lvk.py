@@ -124,6 +124,8 @@ _sig("lvk_seq_count", C.c_int, [C.c_void_p])
 _sig("lvk_seq_tokens", C.c_int, [C.c_void_p, C.c_int])
 _sig("lvk_seq_copy", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int])
 _sig("lvk_decode_batch", C.c_int, [C.c_void_p, i32p, i32p, i32p, C.c_int, C.c_void_p, C.c_void_p])
+_sig("lvk_decode_batch_chain", C.c_int, [C.c_void_p, i32p, C.c_int, i32p, i32p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
+_sig("lvk_rows_step", C.c_int, [f32p, C.c_int, C.c_int, i32p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
 _sig("lvk_init_stage", C.c_void_p, [C.c_char_p, llama_context_params, C.c_int, C.c_int])
 _sig("lvk_stage_eval", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int])
 _sig("lvk_stage_get_x", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int])
@@ -240,6 +242,29 @@ class Llama:
         if r != 0:
             raise RuntimeError("lvk_decode_batch failed")
         return lg, am
+
+    def decode_batch_chain(self, forced, seqs, pos, n_steps, digests=False, logits=False):
+        """n_steps batched decode steps in one call, one row per sequence (lvk_decode_batch_chain):
+        forced is [n_forced][n] (or [n]: greedy after the first tokens); row r starts at pos[r] on
+        slot seqs[r] and takes forced[i][r] at step i < n_forced, then its own previous argmax.
+        Returns (tokens int32 [n_steps][n], digests uint64 [n_steps][n] or None, the last step's
+        logits [n][n_vocab] float32 or None)."""
+        s = np.ascontiguousarray(seqs, np.int32).reshape(-1)
+        p = np.ascontiguousarray(pos, np.int32).reshape(-1)
+        f = np.ascontiguousarray(forced, np.int32)
+        if f.ndim == 1:
+            f = f.reshape(1, -1)
+        if f.ndim != 2 or not (f.shape[1] == len(s) == len(p)):
+            raise ValueError("decode_batch_chain: forced, seqs and pos differ in row count")
+        n, n_steps = len(s), int(n_steps)
+        out = np.zeros((max(n_steps, 0), n), np.int32)
+        dg = np.zeros((max(n_steps, 0), n), np.uint64) if digests else None
+        lg = np.empty((n, self.n_vocab), np.float32) if logits else None
+        r = lib.lvk_decode_batch_chain(self.ctx, f, f.shape[0], s, p, n, n_steps, out.ctypes.data,
+                                       dg.ctypes.data if digests else None, lg.ctypes.data if logits else None)
+        if r != 0:
+            raise RuntimeError("lvk_decode_batch_chain failed")
+        return out, dg, lg
 
     def eval_greedy(self, token, n_past):
         """decode one token and pick the next greedily on the device (lvk_eval_greedy);
@@ -542,6 +567,20 @@ def argmax(x):
     if r < 0:
         raise RuntimeError("lvk_argmax failed")
     return r
+
+
+def rows_step(logits, forced, step):
+    """one launch of the chained batched decode's tail kernel on host logits [n][V] at step index
+    `step` (lvk_rows_step); forced is [n_forced][n] (None or empty: no forced tokens).  Returns
+    (argmax int32 [n], digests uint64 [n], next tokens int32 [n])."""
+    x = np.ascontiguousarray(logits, np.float32)
+    n, v = x.shape
+    f = np.zeros((0, n), np.int32) if forced is None else np.ascontiguousarray(forced, np.int32).reshape(-1, n)
+    am, dg, nt = np.zeros(n, np.int32), np.zeros(n, np.uint64), np.zeros(n, np.int32)
+    fa = f if f.size else np.zeros(1, np.int32)
+    if lib.lvk_rows_step(x, n, v, fa, f.shape[0], int(step), am.ctypes.data, dg.ctypes.data, nt.ctypes.data) != 0:
+        raise RuntimeError("lvk_rows_step failed")
+    return am, dg, nt
 
 
 class _QuantizeFns(C.Structure):      # quantize_fns_t (include/ggml.h, reference ggml.h:808-813)

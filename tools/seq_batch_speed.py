@@ -8,7 +8,10 @@ others), and is repeated at the same positions (a rewind).  Per S: the median st
 `steps` steps after 3 warm-up steps, with the logits rows copied out and with only the device
 argmax; aggregate tok/s = S / step time.  The yardstick is llama_eval (the captured decode graph)
 on slot 0 at the 64 positions.  The per-class device profile is taken at S = 16.  Appends one
-record per model to the JSON file (default profiles/seq_batch_speed.json) and prints it."""
+record per model to the JSON file (default profiles/seq_batch_speed.json) and prints it.
+--chain [--repeats R] [--parent FILE ...]: the chained leg instead (run_chain): lvk_decode_batch_chain
+against the host-fed legs, every leg R times, into profiles/seq_chain_speed.json; FILEs are records
+this tool wrote at the parent commit."""
 import json
 import os
 import sys
@@ -99,21 +102,124 @@ def run(name, steps):
     return rec
 
 
+def spread_pct(v):
+    """run-to-run spread of repeated medians: (max - min) / median, in percent"""
+    return round((max(v) - min(v)) / float(np.median(v)) * 100, 2)
+
+
+def run_chain(name, steps, repeats, parents):
+    """the chained leg (--chain): per S, `steps` steps of S rows in one lvk_decode_batch_chain call
+    (3 warm-up steps in a call of their own, which also builds the step graph for S rows), per-step
+    time = call time / steps, against the host-fed lvk_decode_batch legs of run() measured in this
+    process: same slots, same window filling, the chain starting at min(position, n_ctx - steps) and
+    moving on from there where the host-fed legs rewind.  Two further legs: the chain with the graph
+    off (the same launches enqueued eagerly), and the host-fed argmax-only loop timed as the chain
+    is (the whole of `steps` steps / steps).  Every leg is repeated `repeats` times;
+    the figures are medians over the repeats, the spread is (max - min) / median.  parents: records
+    written by this tool at the parent commit (their host-fed legs, one file per repeat)."""
+    fn, cfg = CFG[name]
+    path = os.path.join('/tmp/lvk_bench', fn)
+    if not os.path.exists(path):
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        lvk.gen_model(path, vocab=os.path.join(ROOT, 'tests', 'golden', 'vocab32000.bin'), **cfg)
+    sweep = [1, 2, 4, 8, 16, 32, 64] if name == '7b' else [16]
+    m = lvk.Llama(path, n_ctx=N_CTX)
+    toks = np.array([1] + [100 + (i * 7919) % 31000 for i in range(1, N_CTX - 1)], np.int32)
+    m.eval(toks, 0)
+    m.seq_init(1 + max(sweep))
+    row_tok = [int(100 + (s * 104729) % 31000) for s in range(N_SLOT)]
+    pos64 = spread(N_SLOT)
+    for p in pos64[:8]:
+        m.eval([row_tok[0]], p)
+    ts = []
+    for i, p in enumerate(pos64):
+        t0 = time.perf_counter()
+        m.eval([row_tok[i]], p)
+        ts.append(time.perf_counter() - t0)
+    single = {'positions': len(pos64), 'tok_s': round(len(ts) / sum(ts), 1), 'median_ms': round(float(np.median(ts)) * 1e3, 3)}
+    m.eval(toks, 0)
+    model = name + ' synthetic'
+    prec = [[r for r in json.load(open(f)) if r['model'] == model] for f in parents]
+    prec = [r[0] for r in prec if r]
+    rec = {'model': model, 'n_ctx': N_CTX, 'steps': steps, 'repeats': repeats, 'weight_bytes': m.weight_bytes(),
+           'single_sequence_llama_eval': single, 'parent_commit_repeats': len(prec), 'chain': []}
+    for S in sweep:
+        pos = spread(S)
+        for s, p in enumerate(pos):
+            m.seq_copy(1 + s, 0, p)
+        seqs = [1 + s for s in range(S)]
+        cpos = [min(p, N_CTX - steps) for p in pos]
+        host, host_am, chain, eager, loop = [], [], [], [], []
+
+        def loop_ms():
+            # the host-fed loop timed as the chain is: the whole of `steps` argmax-only steps / steps
+            for _ in range(3):
+                m.decode_batch(row_tok[:S], seqs, pos, logits=False, argmax=True)
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                m.decode_batch(row_tok[:S], seqs, pos, logits=False, argmax=True)
+            return (time.perf_counter() - t0) / steps * 1e3
+
+        def chain_ms():
+            m.decode_batch_chain(row_tok[:S], seqs, cpos, 3)
+            t0 = time.perf_counter()
+            m.decode_batch_chain(row_tok[:S], seqs, cpos, steps)
+            return (time.perf_counter() - t0) / steps * 1e3
+
+        for _ in range(repeats):
+            host.append(median_ms(lambda: m.decode_batch(row_tok[:S], seqs, pos), steps))
+            host_am.append(median_ms(lambda: m.decode_batch(row_tok[:S], seqs, pos, logits=False, argmax=True), steps))
+            loop.append(loop_ms())
+            chain.append(chain_ms())
+            m.set_graph(0)          # the same launches enqueued eagerly
+            eager.append(chain_ms())
+            m.set_graph(1)
+        h, ha, c = float(np.median(host)), float(np.median(host_am)), float(np.median(chain))
+        line = {'S': S, 'host_fed_step_ms': round(h, 3), 'host_fed_argmax_only_step_ms': round(ha, 3),
+                'host_fed_spread_pct': spread_pct(host), 'host_fed_argmax_only_spread_pct': spread_pct(host_am),
+                'chain_step_ms': round(c, 3), 'chain_spread_pct': spread_pct(chain), 'chain_tok_s': round(S / c * 1e3, 1),
+                'chain_vs_host_fed_argmax_only': round(ha / c, 3), 'chain_vs_host_fed': round(h / c, 3),
+                'chain_vs_single': round(S / c * 1e3 / single['tok_s'], 2),
+                'chain_graph_off_step_ms': round(float(np.median(eager)), 3), 'chain_graph_off_spread_pct': spread_pct(eager),
+                'host_fed_loop_step_ms': round(float(np.median(loop)), 3), 'host_fed_loop_spread_pct': spread_pct(loop),
+                'chain_vs_host_fed_loop': round(float(np.median(loop)) / c, 3)}
+        pl = [[b for b in r['batch'] if b['S'] == S] for r in prec]
+        pl = [b[0] for b in pl if b]
+        if pl:
+            ph, pa = [b['step_ms'] for b in pl], [b['argmax_only_step_ms'] for b in pl]
+            line['parent_host_fed_step_ms'] = round(float(np.median(ph)), 3)
+            line['parent_host_fed_argmax_only_step_ms'] = round(float(np.median(pa)), 3)
+            line['parent_host_fed_spread_pct'] = spread_pct(ph)
+            line['parent_host_fed_argmax_only_spread_pct'] = spread_pct(pa)
+            line['chain_vs_parent_host_fed_argmax_only'] = round(float(np.median(pa)) / c, 3)
+        rec['chain'].append(line)
+        print(json.dumps(line), flush=True)
+    m.close()
+    return rec
+
+
 def main():
     args = sys.argv[1:]
-    steps, out = 20, os.path.join(ROOT, 'profiles', 'seq_batch_speed.json')
-    names = []
+    steps, out = 20, None
+    names, chain, repeats, parents = [], False, 3, []
     while args:
         a = args.pop(0)
         if a == '--steps':
             steps = int(args.pop(0))
         elif a == '--out':
             out = args.pop(0)
+        elif a == '--chain':
+            chain = True
+        elif a == '--repeats':
+            repeats = int(args.pop(0))
+        elif a == '--parent':
+            parents.append(args.pop(0))
         else:
             names.append(a)
+    out = out or os.path.join(ROOT, 'profiles', 'seq_chain_speed.json' if chain else 'seq_batch_speed.json')
     recs = json.load(open(out)) if os.path.exists(out) else []
     for name in names or ['7b']:
-        rec = run(name, steps)
+        rec = run_chain(name, steps, repeats, parents) if chain else run(name, steps)
         recs = [r for r in recs if r['model'] != rec['model']] + [rec]
         print(json.dumps(rec), flush=True)
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
