@@ -236,6 +236,49 @@ LVK_API int lvk_decode_batch_chain(struct llama_context * ctx, const int * force
  * forced [n_forced][n] / n_forced as above.  Writes amax[n], digest[n], next_tok[n].  0 / -1. */
 LVK_API int lvk_rows_step(const float * logits, int n, int V, const int * forced, int n_forced, int step,
                           int * amax, uint64_t * digest, int * next_tok);
+/* A batched decode step that ends in the reference's sampler, per row.  Every slot has its own
+ * mt19937: slot 0 draws from the context's (the one llama_sample_top_p_top_k and lvk_eval_sample
+ * draw from, so the three share one stream), slots >= 1 get theirs at lvk_seq_init, seeded with
+ * the context's seed (llama_context_params.seed as resolved at init).  lvk_seq_copy leaves the
+ * generators alone; lvk_seq_seed reseeds one.
+ *
+ * lvk_decode_batch_sample is lvk_decode_batch(ctx, tokens, seqs, pos, n, NULL, NULL), then for every
+ * row i with rows[i].sample != 0: out_tokens[i] = what llama_sample_top_p_top_k(., last_n, n_last,
+ * top_k, top_p, temp, repeat_penalty) returns on row i's logits (llama.cpp:1356-1459), drawing from
+ * slot seqs[i]'s generator; temp <= 0 is the first-maximum argmax and draws nothing.  Rows with
+ * sample == 0 (prefill rows) give out_tokens[i] = -1.  Several sampled rows of one sequence draw in
+ * row order.  last_n is the caller's window, as llama_sample_top_p_top_k takes it.
+ * The repeat penalty, the temperature and the top-k selection of all sampled rows run in one launch
+ * over the logits in HBM (sample.hip, one workgroup per row); only each row's candidates >= its
+ * k-th value cross PCIe and the host finishes the reference's softmax / top-p /
+ * discrete_distribution over k values per row.  A row with ties among its candidates, NaN logits,
+ * top_k <= 0 or > 1024, or a window > 1024 takes the reference path over all of its logits (that
+ * row alone is copied to the host; same result, slower; counted by lvk_sample_fallbacks).
+ * Every argument is checked before anything is enqueued (lvk_decode_batch's checks; n_last >= 0 and
+ * last_n != NULL when n_last > 0 for every sampled row; out_tokens != NULL): 0, or -1 with a message
+ * on stderr and the context, every slot and every generator unchanged.  The contexts that refuse
+ * lvk_seq_init refuse this call.  llama_get_logits is NOT refreshed.  The rows count into the eval
+ * timings, the sampled rows into the sample timings. */
+struct lvk_row_sample {
+    int sample;            /* 0: no token wanted (prefill rows), out_tokens[i] = -1 */
+    int top_k; float top_p; float temp; float repeat_penalty;
+    int n_last; const int * last_n;      /* the caller's window, as llama_sample_top_p_top_k takes it */
+};
+LVK_API int lvk_decode_batch_sample(struct llama_context * ctx, const int * tokens, const int * seqs, const int * pos,
+                                    int n, const struct lvk_row_sample * rows, int * out_tokens);
+/* reseed a slot's generator (0: the context's rng); seed <= 0 is time(), as at init.  0, -1 on a bad id */
+LVK_API int lvk_seq_seed(struct llama_context * ctx, int seq, int seed);
+/* lvk_eval_sample calls and lvk_decode_batch_sample rows so far that took the all-logits path */
+LVK_API int lvk_sample_fallbacks(struct llama_context * ctx);
+/* op level, on host arrays: the rows kernel (sample.hip) on x[n_rows][n] for the selected rows
+ * sel[n_sel] (row indices, any order, any subset).  Selected row j has k[j] (1..min(n, 1024)),
+ * temp[j] (> 0), rp[j] and the last ids last[last_off[j] .. last_off[j + 1]) (at most 1024; last_off
+ * has n_sel + 1 ascending entries).  Outputs per selected row, as lvk_sample_candidates gives them
+ * for one: vals / ids [n_sel][1024] (the first min(counts[j], 1024) of a row are written),
+ * counts[n_sel], flags[n_sel].  0, -1 on bad arguments. */
+LVK_API int lvk_sample_candidates_rows(const float * x, int n_rows, int n, const int * sel, int n_sel, const int * k,
+                                       const float * temp, const float * rp, const int * last, const int * last_off,
+                                       float * vals, int * ids, int * counts, int * flags);
 
 /* Pipeline stages (the 65B layer split).  A stage context holds
  * layers [layer_begin, layer_end) of the model file (weights and KV cache); the

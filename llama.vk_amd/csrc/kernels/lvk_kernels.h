@@ -387,6 +387,19 @@ struct SampleOut {
     int id[SAMPLE_CAP];
 };
 hipError_t launch_sample_cand(const float * logits, int n, const SampleParams * P, SampleOut * out, hipStream_t s);
+// the same for n_sel rows of logits[.][n] in one launch, one workgroup per record: rec[j] names
+// its logits row and holds its parameters (the SampleParams limits per row), its last-n ids are
+// pool[last_off .. last_off + n_last), its candidates go to out[j] (host-mapped)
+struct SampleRow {
+    int row;                  // index into logits[.][n]
+    int k;                    // top_k (1..SAMPLE_CAP)
+    int n_last;               // entries of its window (0..SAMPLE_MAX_LAST)
+    int last_off;             // the window's offset in the pool
+    float scale;              // 1.0f / temp
+    float rp;                 // repeat_penalty
+};
+hipError_t launch_sample_cand_rows(const float * logits, int n, const SampleRow * rec, const int * pool, int n_sel,
+                                   SampleOut * out, hipStream_t s);
 
 // y[t] = g * rms_norm(x[t]) as f32 (the embeddings output, llama.cpp:1117-1124)
 hipError_t launch_rmsnorm_rows(const float * x, const float * g, int K, int n, float * y, hipStream_t s);

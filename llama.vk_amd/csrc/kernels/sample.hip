@@ -12,6 +12,9 @@
 // (expf, double sums, top-p, the RNG draw) runs unchanged on the host over k values.
 // Ties, NaNs or more candidates than the cap are flagged and the caller falls back to the
 // reference path over all logits (so the result is the reference's in every case).
+// k_sample_cand is one row with its 4 KB parameter block (lvk_eval_sample); k_sample_cand_rows
+// is one workgroup per sampled row of a batched decode step, each with its own compact record,
+// its own window in a flat pool of last-n ids and its own SampleOut.
 #include "lvk_device.h"
 #include "lvk_kernels.h"
 
@@ -31,23 +34,23 @@ __device__ __forceinline__ float keyf(unsigned k) {
     return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
 }
 
-__global__ __launch_bounds__(ST) void k_sample_cand(const float * __restrict__ x, int n,
-                                                    const SampleParams * __restrict__ P, SampleOut * out) {
+// one workgroup, one logits row x[0..n): the candidates of that row into *out.  The body of both
+// kernels below; every word it reads or writes belongs to its own row.
+__device__ __forceinline__ void sample_cand_row(const float * __restrict__ x, int n, int k, int nl,
+                                                const int * __restrict__ last, float scale, float rp, SampleOut * out) {
     __shared__ unsigned bits[SAMPLE_MAX_VOCAB / 32];
     __shared__ unsigned hist[256];
     __shared__ unsigned s_prefix, s_rem, s_count, s_flags;
     const int tid = threadIdx.x;
     for (int i = tid; i < (n + 31) / 32; i += ST) bits[i] = 0u;
-    if (tid == 0) { s_prefix = 0u; s_count = 0u; s_flags = 0u; s_rem = (unsigned) P->k; }
+    if (tid == 0) { s_prefix = 0u; s_count = 0u; s_flags = 0u; s_rem = (unsigned) k; }
     __syncthreads();
-    const int nl = P->n_last;
     for (int i = tid; i < nl; i += ST) {
-        const int t = P->last[i];
+        const int t = last[i];
         if (t >= 0 && t < n) atomicOr(&bits[t >> 5], 1u << (t & 31));
     }
     __syncthreads();
     // the reference's values (llama.cpp:1400-1414): plogits[i]*scale, then *rp or /rp
-    const float scale = P->scale, rp = P->rp;
     float v[PER];
     unsigned key[PER];
     bool nan = false;
@@ -109,11 +112,32 @@ __global__ __launch_bounds__(ST) void k_sample_cand(const float * __restrict__ x
     }
 }
 
+__global__ __launch_bounds__(ST) void k_sample_cand(const float * __restrict__ x, int n,
+                                                    const SampleParams * __restrict__ P, SampleOut * out) {
+    sample_cand_row(x, n, P->k, P->n_last, P->last, P->scale, P->rp, out);
+}
+
+// workgroup j: row rec[j].row of logits[.][n] with rec[j]'s parameters and its window
+// pool[rec[j].last_off ..), candidates into out[j]
+__global__ __launch_bounds__(ST) void k_sample_cand_rows(const float * __restrict__ logits, int n,
+                                                         const SampleRow * __restrict__ rec,
+                                                         const int * __restrict__ pool, SampleOut * out) {
+    const SampleRow r = rec[blockIdx.x];
+    sample_cand_row(logits + (size_t) r.row * n, n, r.k, r.n_last, pool + r.last_off, r.scale, r.rp, out + blockIdx.x);
+}
+
 }  // namespace
 
 hipError_t launch_sample_cand(const float * logits, int n, const SampleParams * P, SampleOut * out, hipStream_t s) {
     if (n <= 0 || n > SAMPLE_MAX_VOCAB) return hipErrorInvalidValue;
     LVK_LAUNCH(k_sample_cand, dim3(1), dim3(ST), 0, s, logits, n, P, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_sample_cand_rows(const float * logits, int n, const SampleRow * rec, const int * pool, int n_sel,
+                                   SampleOut * out, hipStream_t s) {
+    if (n <= 0 || n > SAMPLE_MAX_VOCAB || n_sel <= 0 || !rec || !pool || !out) return hipErrorInvalidValue;
+    LVK_LAUNCH(k_sample_cand_rows, dim3(n_sel), dim3(ST), 0, s, logits, n, rec, pool, out);
     return hipGetLastError();
 }
 

@@ -93,21 +93,16 @@ std::vector<int> tokenize(const lvk::Vocab & vocab, const std::string & text, bo
     return out;
 }
 
-// ---------------------------------------------------------------------------
-// sampler (llama.cpp:1352-1459)
-// ---------------------------------------------------------------------------
-int sample_from_top_k(lvk::Context & c, std::vector<std::pair<float, int>> & cand, float top_p);
+}  // namespace
 
-int sample_top_p_top_k(lvk::Context & c, const std::vector<int> & last, int top_k, float top_p, float temp,
-                       float repeat_penalty) {
-    const int n_logits = (int) c.model.hp.n_vocab;
-    if (!c.logits_valid || c.logits.size() < (size_t) n_logits) {
-        // no eval has left host logits (none yet, a failed eval, or lvk_eval_greedy, which
-        // keeps them on the device): nothing to sample from
-        fprintf(stderr, "llama_sample_top_p_top_k: no logits (call llama_eval first)\n");
-        return -1;
-    }
-    const float * pl = c.logits.data() + c.logits.size() - n_logits;
+// ---------------------------------------------------------------------------
+// sampler (llama.cpp:1352-1459); declared in lvk_context.h
+// ---------------------------------------------------------------------------
+namespace lvk {
+
+// llama_sample_top_p_top_k on the n_logits values at pl, drawing from rng
+int sample_logits(const float * pl, int n_logits, const int * last, int n_last, int top_k, float top_p, float temp,
+                  float repeat_penalty, std::mt19937 & rng) {
     if (temp <= 0) {
         float best = pl[0];
         int id = 0;
@@ -121,8 +116,8 @@ int sample_top_p_top_k(lvk::Context & c, const std::vector<int> & last, int top_
     // membership in last_n as a flag per id: the reference's std::find per logit
     // (llama.cpp:1404) costs n_vocab * last_n compares (~2M at 32000 x 64)
     std::vector<uint8_t> in_last((size_t) n_logits, 0);
-    for (const int t : last)
-        if (t >= 0 && t < n_logits) in_last[(size_t) t] = 1;
+    for (int j = 0; j < n_last; ++j)
+        if (last[j] >= 0 && last[j] < n_logits) in_last[(size_t) last[j]] = 1;
     for (int i = 0; i < n_logits; ++i) {
         if (in_last[(size_t) i]) {
             if (pl[i] < 0.0f) cand.emplace_back(pl[i] * scale * repeat_penalty, i);
@@ -135,13 +130,13 @@ int sample_top_p_top_k(lvk::Context & c, const std::vector<int> & last, int top_
     std::partial_sort(cand.begin(), cand.begin() + k, cand.end(),
                       [](const std::pair<float, int> & a, const std::pair<float, int> & b) { return a.first > b.first; });
     cand.resize(k);
-    return sample_from_top_k(c, cand, top_p);
+    return sample_from_top_k(rng, cand, top_p);
 }
 
 // the reference's sampler after sample_top_k (llama.cpp:1419-1456): softmax over the k
 // candidates in descending order (expf, double sum), the top-p cut, std::discrete_distribution
-// over the context's mt19937
-int sample_from_top_k(lvk::Context & c, std::vector<std::pair<float, int>> & cand, float top_p) {
+// over the given mt19937
+int sample_from_top_k(std::mt19937 & rng, std::vector<std::pair<float, int>> & cand, float top_p) {
     std::vector<float> probs;
     probs.reserve(cand.size());
     const float maxl = cand[0].first;
@@ -164,7 +159,42 @@ int sample_from_top_k(lvk::Context & c, std::vector<std::pair<float, int>> & can
         }
     }
     std::discrete_distribution<> dist(probs.begin(), probs.end());
-    return cand[dist(c.rng)].second;
+    return cand[dist(rng)].second;
+}
+
+// the host tail over one row's device candidates (sample.hip): sorted descending, and when all
+// their values are distinct -- the order is then the one std::partial_sort leaves -- cut to k
+// and handed to sample_from_top_k.  -1, with rng untouched, when the row has to take the
+// all-logits path: a flag, fewer than k or more than SAMPLE_CAP candidates, or a tie anywhere
+// among them (their order would be the heap's)
+int sample_from_candidates(const SampleOut & so, int k, float top_p, std::mt19937 & rng) {
+    if (so.flags != 0 || so.count < k || so.count > SAMPLE_CAP) return -1;
+    std::vector<std::pair<float, int>> cand;
+    cand.reserve((size_t) so.count);
+    for (int i = 0; i < so.count; ++i) cand.emplace_back(so.val[i], so.id[i]);
+    std::sort(cand.begin(), cand.end(),
+              [](const std::pair<float, int> & a, const std::pair<float, int> & b) { return a.first > b.first; });
+    for (size_t i = 1; i < cand.size(); ++i)
+        if (cand[i - 1].first == cand[i].first) return -1;
+    cand.resize((size_t) k);
+    return sample_from_top_k(rng, cand, top_p);
+}
+
+}  // namespace lvk
+
+namespace {
+
+int sample_top_p_top_k(lvk::Context & c, const std::vector<int> & last, int top_k, float top_p, float temp,
+                       float repeat_penalty) {
+    const int n_logits = (int) c.model.hp.n_vocab;
+    if (!c.logits_valid || c.logits.size() < (size_t) n_logits) {
+        // no eval has left host logits (none yet, a failed eval, or lvk_eval_greedy, which
+        // keeps them on the device): nothing to sample from
+        fprintf(stderr, "llama_sample_top_p_top_k: no logits (call llama_eval first)\n");
+        return -1;
+    }
+    return lvk::sample_logits(c.logits.data() + c.logits.size() - n_logits, n_logits, last.data(), (int) last.size(),
+                              top_k, top_p, temp, repeat_penalty, c.rng);
 }
 
 void default_progress(float progress, void * ud) {
@@ -236,6 +266,7 @@ static llama_context * init_context(const char * path_model, struct llama_contex
     lvk::Context & c = ctx->c;
     c.t_start_us = lvk::now_us();
     if (params.seed <= 0) params.seed = (int) time(nullptr);
+    c.seed = params.seed;
     c.rng = std::mt19937(params.seed);
     unsigned cur_pct = 0;
     if (!params.progress_callback) {
@@ -586,23 +617,8 @@ int lvk_eval_sample(struct llama_context * ctx, int token, int n_past, const int
     c.t_eval_us += lvk::now_us() - t0;
     c.n_eval++;
     t0 = lvk::now_us();
-    const lvk::SampleOut & so = *c.sout_h;
-    std::vector<std::pair<float, int>> cand;
-    bool exact = so.flags == 0 && so.count >= k && so.count <= lvk::SAMPLE_CAP;
-    if (exact) {
-        cand.reserve((size_t) so.count);
-        for (int i = 0; i < so.count; ++i) cand.emplace_back(so.val[i], so.id[i]);
-        std::sort(cand.begin(), cand.end(),
-                  [](const std::pair<float, int> & a, const std::pair<float, int> & b) { return a.first > b.first; });
-        // distinct values: the descending order is the one std::partial_sort leaves; a tie
-        // anywhere among the candidates (their order is the heap's) takes the reference path
-        for (size_t i = 1; i < cand.size() && exact; ++i) exact = cand[i - 1].first != cand[i].first;
-    }
-    int r;
-    if (exact) {
-        cand.resize((size_t) k);
-        r = sample_from_top_k(c, cand, top_p);
-    } else {
+    int r = lvk::sample_from_candidates(*c.sout_h, k, top_p, c.rng);
+    if (r < 0) {
         try {
             c.fetch_logits();
         } catch (const lvk::Error & e) {

@@ -19,6 +19,7 @@
 #include <cstring>
 
 #include "../../../include/llama.h"
+#include "../../../include/lvk_ops.h"
 
 namespace lvk {
 
@@ -72,6 +73,10 @@ Context::~Context() {
     for (void * p : {(void *) rc_tok_d, (void *) rc_dig_d, (void *) rc_forced_d, (void *) rc_ctl_d})
         if (p) (void) hipFree(p);
     for (void * p : {(void *) rc_tok_h, (void *) rc_dig_h, (void *) rc_forced_h, (void *) rc_ctl_h})
+        if (p) (void) hipHostFree(p);
+    for (void * p : {(void *) sr_rec_d, (void *) sr_pool_d})
+        if (p) (void) hipFree(p);
+    for (void * p : {(void *) sr_out_h, (void *) sr_rec_h, (void *) sr_pool_h})
         if (p) (void) hipHostFree(p);
     if (chain_h) (void) hipHostFree(chain_h);
     if (chain_ctl_h) (void) hipHostFree(chain_ctl_h);
@@ -724,6 +729,11 @@ void Context::seq_init(int n_seq) {
         LVK_HIP(hipMemset(s.kc, 0, bytes));
         LVK_HIP(hipMemset(s.vc, 0, bytes));
     }
+    // the new slots' generators start from the context's seed; the existing ones stay as they are
+    std::vector<std::mt19937> gens;
+    gens.reserve((size_t) want - 1);
+    gens.assign(seq_rng.begin(), seq_rng.end());
+    gens.resize((size_t) want - 1, std::mt19937((unsigned) seed));
     std::vector<SeqSlot> table;
     table.push_back({kc, vc});
     for (const SeqKV & s : seq_kv) table.push_back({s.kc, s.vc});
@@ -749,6 +759,7 @@ void Context::seq_init(int n_seq) {
         fresh.host = nullptr;
     }
     seq_kv.insert(seq_kv.end(), add.begin(), add.end());
+    seq_rng.swap(gens);
     fresh.dev.clear();
 }
 
@@ -768,25 +779,34 @@ void Context::seq_copy(int dst, int src, int n_tokens) {
     seq_n(dst) = n_tokens;
 }
 
+// the argument checks of a batched decode step (decode_rows, decode_rows_sample), messages under
+// the caller's name
+std::vector<int> Context::rows_check(const char * fn, const int * tokens, const int * seqs, const int * pos, int n) {
+    const int V = (int) model.hp.n_vocab;
+    const std::string f = std::string(fn) + ": ";
+    if (!tokens || !seqs || !pos) throw Error(f + "null argument");
+    if (n < 1 || n > n_ctx_user) throw Error(f + "the row count must be in 1..n_ctx");
+    // next[s]: the position the next row of slot s must have (-1: no row yet)
+    std::vector<int> next((size_t) seq_count(), -1);
+    for (int i = 0; i < n; ++i) {
+        if (tokens[i] < 0 || tokens[i] >= V) throw Error(f + "token id out of range");
+        if (seqs[i] < 0 || seqs[i] >= seq_count()) throw Error(f + "sequence id out of range");
+        if (pos[i] < 0 || pos[i] >= n_ctx_user) throw Error(f + "position outside n_ctx");
+        int & nx = next[(size_t) seqs[i]];
+        if (nx < 0 && pos[i] > seq_n(seqs[i])) throw Error(f + "position past the end of its sequence (a hole)");
+        if (nx >= 0 && pos[i] != nx) throw Error(f + "rows of one sequence must have consecutive ascending positions");
+        nx = pos[i] + 1;
+    }
+    return next;
+}
+
 // One batched decode step (lvk_decode_batch).  Every argument is checked before anything is
 // enqueued; the slots' counts move only after the step has completed.
 void Context::decode_rows(const int * tokens, const int * seqs, const int * pos, int n, float * logits_out, int * argmax_out) {
     const HParams & hp = model.hp;
     const int V = (int) hp.n_vocab;
     if (!slots_d) seq_init(1);
-    if (!tokens || !seqs || !pos) throw Error("lvk_decode_batch: null argument");
-    if (n < 1 || n > n_ctx_user) throw Error("lvk_decode_batch: the row count must be in 1..n_ctx");
-    // next[s]: the position the next row of slot s must have (-1: no row yet)
-    std::vector<int> next((size_t) seq_count(), -1);
-    for (int i = 0; i < n; ++i) {
-        if (tokens[i] < 0 || tokens[i] >= V) throw Error("lvk_decode_batch: token id out of range");
-        if (seqs[i] < 0 || seqs[i] >= seq_count()) throw Error("lvk_decode_batch: sequence id out of range");
-        if (pos[i] < 0 || pos[i] >= n_ctx_user) throw Error("lvk_decode_batch: position outside n_ctx");
-        int & nx = next[(size_t) seqs[i]];
-        if (nx < 0 && pos[i] > seq_n(seqs[i])) throw Error("lvk_decode_batch: position past the end of its sequence (a hole)");
-        if (nx >= 0 && pos[i] != nx) throw Error("lvk_decode_batch: rows of one sequence must have consecutive ascending positions");
-        nx = pos[i] + 1;
-    }
+    const std::vector<int> next = rows_check("lvk_decode_batch", tokens, seqs, pos, n);
     try {
         if (sp_next > n_ctx) throw Error("llama.vk_amd: too many slices before a sync");
         StepParams * sh = sp_h + sp_next++;
@@ -817,6 +837,172 @@ void Context::decode_rows(const int * tokens, const int * seqs, const int * pos,
     logits_valid = valid;
     for (int s = 0; s < seq_count(); ++s)
         if (next[(size_t) s] >= 0) seq_n(s) = next[(size_t) s];
+}
+
+// room for `rows` sampled rows of a step and `pool` last-n ids: the host-mapped candidates, the
+// records and the pool, on the device and page-locked on the host.  Everything new is allocated
+// before anything is committed (as rows_chain_reserve); a buffer that is large enough stays.
+void Context::rows_sample_reserve(size_t rows, size_t pool) {
+    const bool grow_rows = rows > sr_cap, grow_pool = pool > sr_pool_cap || !sr_pool_d;
+    if (!grow_rows && !grow_pool) return;
+    struct Fresh {      // freed unless committed
+        std::vector<void *> dev, host;
+        ~Fresh() {
+            for (void * p : dev) (void) hipFree(p);
+            for (void * p : host) (void) hipHostFree(p);
+        }
+        void * get(size_t n, int kind) {      // 0 device, 1 pinned, 2 host-mapped
+            void * p = nullptr;
+            const hipError_t e = kind == 0 ? hipMalloc(&p, n)
+                                           : hipHostMalloc(&p, n, kind == 1 ? hipHostMallocDefault
+                                                                            : hipHostMallocMapped | hipHostMallocCoherent);
+            if (e != hipSuccess) {
+                (void) hipGetLastError();
+                throw Error("lvk_decode_batch_sample: out of memory for the sampler's rows");
+            }
+            (kind == 0 ? dev : host).push_back(p);
+            return p;
+        }
+    } fresh;
+    const size_t rcap = grow_rows ? std::max(rows, (size_t) 16) : sr_cap;
+    const size_t pcap = grow_pool ? std::max(std::max(pool, sr_pool_cap), (size_t) 1024) : sr_pool_cap;
+    SampleOut * out_hn = sr_out_h, * out_dn = sr_out_d;
+    SampleRow * rec_hn = sr_rec_h, * rec_dn = sr_rec_d;
+    int * pool_hn = sr_pool_h, * pool_dn = sr_pool_d;
+    if (grow_rows) {
+        out_hn = (SampleOut *) fresh.get(rcap * sizeof(SampleOut), 2);
+        LVK_HIP(hipHostGetDevicePointer((void **) &out_dn, out_hn, 0));
+        rec_hn = (SampleRow *) fresh.get(rcap * sizeof(SampleRow), 1);
+        rec_dn = (SampleRow *) fresh.get(rcap * sizeof(SampleRow), 0);
+    }
+    if (grow_pool) {
+        pool_hn = (int *) fresh.get(pcap * sizeof(int), 1);
+        pool_dn = (int *) fresh.get(pcap * sizeof(int), 0);
+    }
+    LVK_HIP(hipStreamSynchronize(stream));      // nothing in flight uses the old buffers
+    // commit
+    if (grow_rows) {
+        if (sr_rec_d) (void) hipFree(sr_rec_d);
+        for (void * p : {(void *) sr_out_h, (void *) sr_rec_h})
+            if (p) (void) hipHostFree(p);
+        sr_out_h = out_hn; sr_out_d = out_dn;
+        sr_rec_h = rec_hn; sr_rec_d = rec_dn;
+        sr_cap = rcap;
+    }
+    if (grow_pool) {
+        if (sr_pool_d) (void) hipFree(sr_pool_d);
+        if (sr_pool_h) (void) hipHostFree(sr_pool_h);
+        sr_pool_h = pool_hn; sr_pool_d = pool_dn;
+        sr_pool_cap = pcap;
+    }
+    fresh.dev.clear();
+    fresh.host.clear();
+}
+
+// One batched decode step that ends in the sampler (lvk_decode_batch_sample): decode_rows' forward
+// pass, enqueued eagerly; launch_argmax_rows over the span of rows that ask for a greedy token
+// (temp <= 0); one launch_sample_cand_rows for the rows that sample within the device limits; one
+// stream sync; then, in row order, the host tail of lvk_eval_sample over each row's candidates
+// with the generator of the row's slot.  A row with ties, NaN, overflow, top_k <= 0 or >
+// SAMPLE_CAP, or a window > SAMPLE_MAX_LAST has its own logits row copied to the host and takes
+// sample_logits there with the same generator (n_sample_fallback counts it); no other row notices.
+// Every argument is checked before anything is enqueued; the slots' counts move after the step
+// has completed.  The rows count into the eval timings, the sampled rows into the sample timings.
+void Context::decode_rows_sample(const int * tokens, const int * seqs, const int * pos, int n, const lvk_row_sample * rows,
+                                 int * out_tokens) {
+    const int64_t t0 = now_us();
+    const int V = (int) model.hp.n_vocab;
+    if (!slots_d) seq_init(1);
+    const std::vector<int> next = rows_check("lvk_decode_batch_sample", tokens, seqs, pos, n);
+    if (!rows || !out_tokens) throw Error("lvk_decode_batch_sample: null argument");
+    enum : char { NONE, GREEDY, DEVICE, HOST };
+    std::vector<char> kind((size_t) n, NONE);
+    std::vector<int> top((size_t) n, 0);      // the reference's k: top_k, or all of them
+    size_t n_dev = 0, n_pool = 0;
+    int n_samp = 0, g_lo = n, g_hi = -1;
+    for (int i = 0; i < n; ++i) {
+        const lvk_row_sample & r = rows[i];
+        if (!r.sample) continue;
+        if (r.n_last < 0 || (r.n_last > 0 && !r.last_n)) throw Error("lvk_decode_batch_sample: bad last-n window");
+        ++n_samp;
+        const int k = top[(size_t) i] = r.top_k > 0 ? std::min(r.top_k, V) : V;
+        if (r.temp <= 0) {                              // llama.cpp:1382-1394
+            kind[(size_t) i] = GREEDY;
+            g_lo = std::min(g_lo, i);
+            g_hi = i;
+        } else if (k > SAMPLE_CAP || r.n_last > SAMPLE_MAX_LAST || V > SAMPLE_MAX_VOCAB) {
+            kind[(size_t) i] = HOST;
+        } else {
+            kind[(size_t) i] = DEVICE;
+            ++n_dev;
+            n_pool += (size_t) r.n_last;
+        }
+    }
+    if (n_dev) rows_sample_reserve(n_dev, n_pool);
+    std::vector<int> amax((size_t) n, -1), slot_of((size_t) n, -1);
+    try {
+        if (sp_next > n_ctx) throw Error("llama.vk_amd: too many slices before a sync");
+        StepParams * sh = sp_h + sp_next++;
+        sh->n_past = 0;             // no kernel of this path takes a position from the step block
+        sh->n_tokens = n;
+        sh->pad0 = n == 1 ? tokens[0] : 0;
+        sh->seq = next_seq();
+        std::memcpy(tok_h, tokens, sizeof(int) * (size_t) n);
+        for (int i = 0; i < n; ++i) rows_h[i] = {seqs[i], pos[i]};
+        size_t j = 0, off = 0;
+        for (int i = 0; i < n; ++i) {
+            if (kind[(size_t) i] != DEVICE) continue;
+            const lvk_row_sample & r = rows[i];
+            sr_rec_h[j] = {i, top[(size_t) i], r.n_last, (int) off, 1.0f / r.temp /* llama.cpp:1398 */, r.repeat_penalty};
+            if (r.n_last > 0) std::memcpy(sr_pool_h + off, r.last_n, sizeof(int) * (size_t) r.n_last);
+            off += (size_t) r.n_last;
+            slot_of[(size_t) i] = (int) j++;
+        }
+        LVK_HIP(hipMemcpyAsync(sp_d, sh, sizeof(StepParams), hipMemcpyHostToDevice, stream));
+        LVK_HIP(hipMemcpyAsync(tok_d, tok_h, sizeof(int) * (size_t) n, hipMemcpyHostToDevice, stream));
+        LVK_HIP(hipMemcpyAsync(rows_d, rows_h, sizeof(SeqRow) * (size_t) n, hipMemcpyHostToDevice, stream));
+        if (n_dev) {
+            LVK_HIP(hipMemcpyAsync(sr_rec_d, sr_rec_h, sizeof(SampleRow) * n_dev, hipMemcpyHostToDevice, stream));
+            if (n_pool) LVK_HIP(hipMemcpyAsync(sr_pool_d, sr_pool_h, sizeof(int) * n_pool, hipMemcpyHostToDevice, stream));
+        }
+        enqueue_forward(n, false, tok_d, 0, true, true, true);
+        if (g_hi >= 0) {
+            const size_t m = (size_t) (g_hi - g_lo + 1);
+            LVK_HIP(launch_argmax_rows(logits_d + (size_t) g_lo * V, V, (int) m, amax_d + g_lo, stream));
+            LVK_HIP(hipMemcpyAsync(amax.data() + g_lo, amax_d + g_lo, sizeof(int) * m, hipMemcpyDeviceToHost, stream));
+        }
+        if (n_dev) LVK_HIP(launch_sample_cand_rows(logits_d, V, sr_rec_d, sr_pool_d, (int) n_dev, sr_out_d, stream));
+    } catch (...) {
+        (void) hipStreamSynchronize(stream);
+        sp_next = 1;
+        throw;
+    }
+    // the host logits of llama_get_logits are an earlier eval's: they stay as they are
+    const bool valid = logits_valid;
+    end_eval(true);
+    logits_valid = valid;
+    for (int s = 0; s < seq_count(); ++s)
+        if (next[(size_t) s] >= 0) seq_n(s) = next[(size_t) s];
+    const int64_t t1 = now_us();
+    t_eval_us += t1 - t0;       // n decode evals (llama.cpp:1186-1195)
+    n_eval += n;
+    std::vector<float> row;
+    for (int i = 0; i < n; ++i) {
+        const lvk_row_sample & r = rows[i];
+        int tok = -1;
+        if (kind[(size_t) i] == GREEDY) tok = amax[(size_t) i];
+        else if (kind[(size_t) i] == DEVICE)
+            tok = sample_from_candidates(sr_out_h[slot_of[(size_t) i]], top[(size_t) i], r.top_p, seq_gen(seqs[i]));
+        if (tok < 0 && (kind[(size_t) i] == DEVICE || kind[(size_t) i] == HOST)) {
+            row.resize((size_t) V);
+            LVK_HIP(hipMemcpy(row.data(), logits_d + (size_t) i * V, sizeof(float) * (size_t) V, hipMemcpyDeviceToHost));
+            tok = sample_logits(row.data(), V, r.last_n, r.n_last, r.top_k, r.top_p, r.temp, r.repeat_penalty, seq_gen(seqs[i]));
+            n_sample_fallback++;
+        }
+        out_tokens[i] = tok;
+    }
+    t_sample_us += now_us() - t1;
+    n_sample += n_samp;
 }
 
 void Context::drop_rows_graph() {

@@ -10,6 +10,7 @@
 #include <new>
 
 struct llama_context_params;
+struct lvk_row_sample;      // include/lvk_ops.h
 
 namespace lvk {
 
@@ -135,7 +136,7 @@ struct Context {
     void eval_sample(int token, int n_past);
     // the last eval's last-token logits row -> host logits (llama_get_logits valid again)
     void fetch_logits();
-    int n_sample_fallback = 0;         // lvk_eval_sample calls that took the all-logits host path
+    int n_sample_fallback = 0;         // lvk_eval_sample calls / lvk_decode_batch_sample rows that took the all-logits host path
     int * greedy_d = nullptr;
     int * greedy_h = nullptr;    // host-mapped (coherent): the device argmax writes it
     int * greedy_hd = nullptr;   // its device address
@@ -184,6 +185,24 @@ struct Context {
                            int * out_tokens, unsigned long long * out_digests, float * logits_out);
     void rows_chain_reserve(size_t entries);
     void drop_rows_graph();
+    // decode_rows' step, then per row with rows[i].sample != 0 the sampler on row i's logits
+    // (lvk_decode_batch_sample): greedy rows through launch_argmax_rows, the others through one
+    // launch_sample_cand_rows and the host tail of lvk_eval_sample per row, in row order, drawing
+    // from the row's slot's generator
+    void decode_rows_sample(const int * tokens, const int * seqs, const int * pos, int n, const lvk_row_sample * rows,
+                            int * out_tokens);
+    // the checks of a batched decode step's rows; next[s]: the count slot s has after the step (-1: no row)
+    std::vector<int> rows_check(const char * fn, const int * tokens, const int * seqs, const int * pos, int n);
+    // per sampled row of a step (sr_cap of them, grown on demand): the candidates (host-mapped)
+    // and the kernel's record; sr_pool_cap ints of last-n windows back to back
+    size_t sr_cap = 0, sr_pool_cap = 0;
+    SampleOut * sr_out_h = nullptr, * sr_out_d = nullptr;
+    SampleRow * sr_rec_h = nullptr, * sr_rec_d = nullptr;   // pinned staging, device
+    int * sr_pool_h = nullptr, * sr_pool_d = nullptr;
+    void rows_sample_reserve(size_t rows, size_t pool);
+    // the generators of slots >= 1 (slot 0 draws from rng), seeded with `seed` at seq_init
+    std::vector<std::mt19937> seq_rng;
+    std::mt19937 & seq_gen(int s) { return s == 0 ? rng : seq_rng[(size_t) s - 1]; }
 
     // host-visible results
     std::vector<float, PinnedAlloc<float>> logits;
@@ -192,6 +211,7 @@ struct Context {
     std::vector<uint8_t> kv_host;
     int kv_n = 0;
     std::mt19937 rng;
+    int seed = 0;                // llama_context_params.seed as resolved at init (<= 0: time())
 
     // timings (llama.cpp:1186-1195)
     int64_t t_start_us = 0, t_load_us = 0, t_sample_us = 0, t_eval_us = 0, t_p_eval_us = 0;
@@ -249,6 +269,12 @@ struct Context {
 };
 
 int64_t now_us();
+// the host sampler (llama_api.cpp): llama_sample_top_p_top_k over n_logits values; its part after
+// the top-k selection; the same over one row's device candidates (-1: take the all-logits path)
+int sample_logits(const float * pl, int n_logits, const int * last, int n_last, int top_k, float top_p, float temp,
+                  float repeat_penalty, std::mt19937 & rng);
+int sample_from_top_k(std::mt19937 & rng, std::vector<std::pair<float, int>> & cand, float top_p);
+int sample_from_candidates(const SampleOut & so, int k, float top_p, std::mt19937 & rng);
 // exp mode of the softmax kernels (lvk_device.h exp_f16): 2, 1 or 0 after a device self-check
 int pick_exp_mode(const uint16_t * exp_tab_d);
 // fp16 exp / silu tables (ggml.c:2915-2927) built with this host's glibc expf

@@ -5,6 +5,7 @@
 
 #include <cstdio>
 #include <cstring>
+#include <ctime>
 #include <vector>
 
 #include "../../../include/llama.h"
@@ -435,6 +436,60 @@ int lvk_decode_batch_chain(struct llama_context * ctx, const int * forced, int n
         c.decode_rows_chain(forced, n_forced, seqs, pos, n, n_steps, out_tokens, (unsigned long long *) out_digests, logits);
         c.t_eval_us += lvk::now_us() - t0;   // n * n_steps decode evals (llama.cpp:1186-1195)
         c.n_eval += n * n_steps;
+        return 0;
+    } catch (const lvk::Error & e) { return fail(__func__, e.msg); }
+}
+
+int lvk_decode_batch_sample(struct llama_context * ctx, const int * tokens, const int * seqs, const int * pos, int n,
+                            const struct lvk_row_sample * rows, int * out_tokens) {
+    try {
+        if (!ctx) throw lvk::Error("null context");
+        if (ctx->split) throw lvk::Error("not available on a layer split");
+        ctx->c.decode_rows_sample(tokens, seqs, pos, n, rows, out_tokens);   // it keeps the timings itself
+        return 0;
+    } catch (const lvk::Error & e) { return fail(__func__, e.msg); }
+}
+
+int lvk_seq_seed(struct llama_context * ctx, int seq, int seed) {
+    if (!ctx || seq < 0 || seq >= ctx->c.seq_count()) return -1;
+    if (seed <= 0) seed = (int) time(nullptr);      // as llama_init_from_file resolves it
+    ctx->c.seq_gen(seq) = std::mt19937((unsigned) seed);
+    return 0;
+}
+
+int lvk_sample_fallbacks(struct llama_context * ctx) { return ctx ? ctx->c.n_sample_fallback : -1; }
+
+int lvk_sample_candidates_rows(const float * x, int n_rows, int n, const int * sel, int n_sel, const int * k,
+                               const float * temp, const float * rp, const int * last, const int * last_off,
+                               float * vals, int * ids, int * counts, int * flags) {
+    try {
+        if (!x || !sel || !k || !temp || !rp || !last_off || !vals || !ids || !counts || !flags || n_rows <= 0 ||
+            n <= 0 || n > lvk::SAMPLE_MAX_VOCAB || n_sel <= 0 || last_off[0] < 0 || (size_t) n_rows * (size_t) n > ((size_t) 1 << 28))
+            throw lvk::Error("arguments out of range");
+        std::vector<lvk::SampleRow> rec((size_t) n_sel);
+        for (int j = 0; j < n_sel; ++j) {
+            const int nl = last_off[j + 1] - last_off[j];
+            if (sel[j] < 0 || sel[j] >= n_rows || k[j] < 1 || k[j] > std::min(n, lvk::SAMPLE_CAP) || !(temp[j] > 0) ||
+                nl < 0 || nl > lvk::SAMPLE_MAX_LAST || (nl > 0 && !last))
+                throw lvk::Error("arguments out of range");
+            rec[(size_t) j] = {sel[j], k[j], nl, last_off[j], 1.0f / temp[j], rp[j]};
+        }
+        Dev dv;
+        float * xd = dv.up(x, (size_t) n_rows * n);
+        lvk::SampleRow * rd = dv.up(rec.data(), rec.size());
+        const size_t n_pool = (size_t) last_off[n_sel];
+        int * pd = n_pool ? dv.up(last, n_pool) : (int *) dv.get(4);
+        auto * od = (lvk::SampleOut *) dv.get((size_t) n_sel * sizeof(lvk::SampleOut));
+        LVK_HIP(lvk::launch_sample_cand_rows(xd, n, rd, pd, n_sel, od, nullptr));
+        std::vector<lvk::SampleOut> o((size_t) n_sel);
+        LVK_HIP(hipMemcpy(o.data(), od, o.size() * sizeof(lvk::SampleOut), hipMemcpyDeviceToHost));
+        for (int j = 0; j < n_sel; ++j) {
+            const size_t m = (size_t) std::min(o[(size_t) j].count, lvk::SAMPLE_CAP);
+            std::memcpy(vals + (size_t) j * lvk::SAMPLE_CAP, o[(size_t) j].val, sizeof(float) * m);
+            std::memcpy(ids + (size_t) j * lvk::SAMPLE_CAP, o[(size_t) j].id, sizeof(int) * m);
+            counts[j] = o[(size_t) j].count;
+            flags[j] = o[(size_t) j].flags;
+        }
         return 0;
     } catch (const lvk::Error & e) { return fail(__func__, e.msg); }
 }

@@ -55,6 +55,19 @@ class llama_context_params(C.Structure):
     ]
 
 
+class lvk_row_sample(C.Structure):
+    """include/lvk_ops.h, field for field"""
+    _fields_ = [
+        ("sample", C.c_int),
+        ("top_k", C.c_int),
+        ("top_p", C.c_float),
+        ("temp", C.c_float),
+        ("repeat_penalty", C.c_float),
+        ("n_last", C.c_int),
+        ("last_n", C.c_void_p),
+    ]
+
+
 def _sig(name, res, args):
     fn = getattr(lib, name)
     fn.restype = res
@@ -125,6 +138,10 @@ _sig("lvk_seq_tokens", C.c_int, [C.c_void_p, C.c_int])
 _sig("lvk_seq_copy", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int])
 _sig("lvk_decode_batch", C.c_int, [C.c_void_p, i32p, i32p, i32p, C.c_int, C.c_void_p, C.c_void_p])
 _sig("lvk_decode_batch_chain", C.c_int, [C.c_void_p, i32p, C.c_int, i32p, i32p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
+_sig("lvk_decode_batch_sample", C.c_int, [C.c_void_p, i32p, i32p, i32p, C.c_int, C.c_void_p, C.c_void_p])
+_sig("lvk_seq_seed", C.c_int, [C.c_void_p, C.c_int, C.c_int])
+_sig("lvk_sample_fallbacks", C.c_int, [C.c_void_p])
+_sig("lvk_sample_candidates_rows", C.c_int, [f32p, C.c_int, C.c_int, i32p, C.c_int, i32p, f32p, f32p, i32p, i32p, f32p, i32p, i32p, i32p])
 _sig("lvk_rows_step", C.c_int, [f32p, C.c_int, C.c_int, i32p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
 _sig("lvk_init_stage", C.c_void_p, [C.c_char_p, llama_context_params, C.c_int, C.c_int])
 _sig("lvk_stage_eval", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int])
@@ -265,6 +282,41 @@ class Llama:
         if r != 0:
             raise RuntimeError("lvk_decode_batch_chain failed")
         return out, dg, lg
+
+    def decode_batch_sample(self, tokens, seqs, pos, samplers):
+        """one step over n rows that ends in the sampler per row (lvk_decode_batch_sample): samplers
+        holds, per row, None (no token wanted) or dict(top_k, top_p, temp, repeat_penalty,
+        last_tokens) with llama_sample_top_p_top_k's meaning (defaults 40, 0.95, 0.8, 1.1, no
+        window); a row draws from its slot's generator.  Returns int32 [n], -1 where none was
+        asked for."""
+        t = np.ascontiguousarray(tokens, np.int32).reshape(-1)
+        s = np.ascontiguousarray(seqs, np.int32).reshape(-1)
+        p = np.ascontiguousarray(pos, np.int32).reshape(-1)
+        if not (len(t) == len(s) == len(p) == len(samplers)):
+            raise ValueError("decode_batch_sample: tokens, seqs, pos and samplers differ in length")
+        rows = (lvk_row_sample * max(len(t), 1))()
+        keep = []       # the windows stay alive over the call
+        for r, sm in zip(rows, samplers):
+            if sm is None:
+                continue
+            lt = np.ascontiguousarray(sm.get("last_tokens", ()), np.int32).reshape(-1)
+            keep.append(lt)
+            r.sample, r.top_k, r.top_p = 1, int(sm.get("top_k", 40)), float(sm.get("top_p", 0.95))
+            r.temp, r.repeat_penalty = float(sm.get("temp", 0.8)), float(sm.get("repeat_penalty", 1.1))
+            r.n_last, r.last_n = len(lt), lt.ctypes.data if len(lt) else None
+        out = np.full(len(t), -1, np.int32)
+        if lib.lvk_decode_batch_sample(self.ctx, t, s, p, len(t), C.addressof(rows), out.ctypes.data) != 0:
+            raise RuntimeError("lvk_decode_batch_sample failed")
+        return out
+
+    def seq_seed(self, seq, seed):
+        """reseed a slot's generator (slot 0: the context's, which sample / eval_sample draw from)"""
+        if lib.lvk_seq_seed(self.ctx, int(seq), int(seed)) != 0:
+            raise RuntimeError("lvk_seq_seed failed")
+
+    def sample_fallbacks(self):
+        """eval_sample calls and decode_batch_sample rows so far that took the all-logits path"""
+        return lib.lvk_sample_fallbacks(self.ctx)
 
     def eval_greedy(self, token, n_past):
         """decode one token and pick the next greedily on the device (lvk_eval_greedy);
@@ -639,6 +691,31 @@ def sample_candidates(x, last, k, temp, rp):
         raise RuntimeError("lvk_sample_candidates failed")
     m = min(n, 1024)
     return vals[:m], ids[:m], fl.value, n
+
+
+def sample_candidates_rows(x, sel, k, temp, rp, last):
+    """lvk_sample_candidates_rows: the rows kernel on x [n_rows][n] for the rows sel (indices, any
+    order); k, temp, rp and last (a list of id lists) per selected row.  Returns, per selected row,
+    (values, ids, flags, count) as sample_candidates gives them."""
+    x = np.ascontiguousarray(x, np.float32)
+    n_rows, n = x.shape
+    sel = np.ascontiguousarray(sel, np.int32).reshape(-1)
+    m = len(sel)
+    k = np.ascontiguousarray(k, np.int32).reshape(-1)
+    temp = np.ascontiguousarray(temp, np.float32).reshape(-1)
+    rp = np.ascontiguousarray(rp, np.float32).reshape(-1)
+    if not (len(k) == len(temp) == len(rp) == len(last) == m):
+        raise ValueError("sample_candidates_rows: per-row arguments differ in length")
+    off = np.zeros(m + 1, np.int32)
+    off[1:] = np.cumsum([len(w) for w in last])
+    pool = np.ascontiguousarray(np.concatenate([np.asarray(w, np.int32).reshape(-1) for w in last] + [np.zeros(1, np.int32)]))
+    vals = np.zeros((max(m, 1), 1024), np.float32)
+    ids = np.zeros((max(m, 1), 1024), np.int32)
+    cnt = np.zeros(max(m, 1), np.int32)
+    fl = np.zeros(max(m, 1), np.int32)
+    if lib.lvk_sample_candidates_rows(x, n_rows, n, sel, m, k, temp, rp, pool, off, vals, ids, cnt, fl) != 0:
+        raise RuntimeError("lvk_sample_candidates_rows failed")
+    return [(vals[j, :min(int(cnt[j]), 1024)], ids[j, :min(int(cnt[j]), 1024)], int(fl[j]), int(cnt[j])) for j in range(m)]
 
 
 def rms_norm_mul(x, g):

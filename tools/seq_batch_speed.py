@@ -11,7 +11,10 @@ on slot 0 at the 64 positions.  The per-class device profile is taken at S = 16.
 record per model to the JSON file (default profiles/seq_batch_speed.json) and prints it.
 --chain [--repeats R] [--parent FILE ...]: the chained leg instead (run_chain): lvk_decode_batch_chain
 against the host-fed legs, every leg R times, into profiles/seq_chain_speed.json; FILEs are records
-this tool wrote at the parent commit."""
+this tool wrote at the parent commit.
+--sample [--repeats R]: the sampled leg instead (run_sample): lvk_decode_batch_sample against the
+argmax-only and the logits-to-host steps at 1, 16 and 64 sequences, into profiles/seq_sample_speed.json."""
+import ctypes
 import json
 import os
 import sys
@@ -198,10 +201,84 @@ def run_chain(name, steps, repeats, parents):
     return rec
 
 
+def run_sample(name, steps, repeats):
+    """the sampled leg (--sample): per S in 1, 16, 64, three legs over the same rows (run()'s slots and
+    positions, rewound every step; the rows' tokens change from step to step, the same way in every
+    leg, so the logits do), called through the C entry points with every argument built beforehand:
+    (a) lvk_decode_batch with the device argmax only;
+    (b) lvk_decode_batch_sample with top_k 40, top_p 0.95, temp 0.8, repeat_penalty 1.1 and a 64-token
+        window per row;
+    (c) lvk_decode_batch with the logits rows copied to the host and nothing done with them: a lower
+        bound on what a sampler on the host costs a caller without (b).
+    Each leg's figure is the median step over `steps` steps after 3 warm-up steps; the legs run one
+    after the other `repeats` times; reported are the medians over the repeats, the run-to-run spread
+    (max - min) / median, the differences (b) - (a) and (c) - (a) per repeat, and the rows of (b) that
+    took the all-logits path."""
+    fn, cfg = CFG[name]
+    path = os.path.join('/tmp/lvk_bench', fn)
+    if not os.path.exists(path):
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        lvk.gen_model(path, vocab=os.path.join(ROOT, 'tests', 'golden', 'vocab32000.bin'), **cfg)
+    sweep = [1, 16, 64]
+    m = lvk.Llama(path, n_ctx=N_CTX)
+    toks = np.array([1] + [100 + (i * 7919) % 31000 for i in range(1, N_CTX - 1)], np.int32)
+    m.eval(toks, 0)
+    m.seq_init(1 + max(sweep))
+    variants = 8
+    row_tok = [np.array([100 + ((s + 64 * v) * 104729) % 31000 for s in range(N_SLOT)], np.int32) for v in range(variants)]
+    wins = [np.ascontiguousarray(toks[7 * s:7 * s + 64]) for s in range(N_SLOT)]     # 64 ids per row, the rows' differ
+    assert all(len(w) == 64 for w in wins)
+    lib = lvk.lib
+    rec = {'model': name + ' synthetic', 'n_ctx': N_CTX, 'steps': steps, 'repeats': repeats, 'weight_bytes': m.weight_bytes(),
+           'sampler': {'top_k': 40, 'top_p': 0.95, 'temp': 0.8, 'repeat_penalty': 1.1, 'window': 64}, 'sample': []}
+    for S in sweep:
+        pos = np.array(spread(S), np.int32)
+        for s, p in enumerate(pos):
+            m.seq_copy(1 + s, 0, int(p))
+        seqs = np.arange(1, S + 1, dtype=np.int32)
+        rows = (lvk.lvk_row_sample * S)(*[lvk.lvk_row_sample(1, 40, 0.95, 0.8, 1.1, 64, wins[s].ctypes.data) for s in range(S)])
+        out = np.zeros(S, np.int32)
+        lg = np.zeros((S, m.n_vocab), np.float32)
+        step = [0]
+
+        def tok():
+            step[0] += 1
+            return np.ascontiguousarray(row_tok[step[0] % variants][:S])
+
+        def leg_a():
+            assert lib.lvk_decode_batch(m.ctx, tok(), seqs, pos, S, None, out.ctypes.data) == 0
+
+        def leg_b():
+            assert lib.lvk_decode_batch_sample(m.ctx, tok(), seqs, pos, S, ctypes.addressof(rows), out.ctypes.data) == 0
+
+        def leg_c():
+            assert lib.lvk_decode_batch(m.ctx, tok(), seqs, pos, S, lg.ctypes.data, None) == 0
+
+        a, b, c = [], [], []
+        f0 = m.sample_fallbacks()
+        for _ in range(repeats):
+            a.append(median_ms(leg_a, steps))
+            b.append(median_ms(leg_b, steps))
+            c.append(median_ms(leg_c, steps))
+        ba, ca = [y - x for x, y in zip(a, b)], [y - x for x, y in zip(a, c)]
+        line = {'S': S, 'argmax_only_step_ms': round(float(np.median(a)), 3), 'argmax_only_spread_pct': spread_pct(a),
+                'sample_step_ms': round(float(np.median(b)), 3), 'sample_spread_pct': spread_pct(b),
+                'logits_to_host_step_ms': round(float(np.median(c)), 3), 'logits_to_host_spread_pct': spread_pct(c),
+                'sample_minus_argmax_ms': round(float(np.median(ba)), 3), 'sample_minus_argmax_ms_repeats': [round(v, 3) for v in ba],
+                'logits_to_host_minus_argmax_ms': round(float(np.median(ca)), 3),
+                'logits_to_host_minus_argmax_ms_repeats': [round(v, 3) for v in ca],
+                'sample_tok_s': round(S / float(np.median(b)) * 1e3, 1),
+                'sampled_rows': S * (steps + 3) * repeats, 'fallback_rows': m.sample_fallbacks() - f0}
+        rec['sample'].append(line)
+        print(json.dumps(line), flush=True)
+    m.close()
+    return rec
+
+
 def main():
     args = sys.argv[1:]
     steps, out = 20, None
-    names, chain, repeats, parents = [], False, 3, []
+    names, chain, repeats, parents, sample = [], False, 3, [], False
     while args:
         a = args.pop(0)
         if a == '--steps':
@@ -210,16 +287,20 @@ def main():
             out = args.pop(0)
         elif a == '--chain':
             chain = True
+        elif a == '--sample':
+            sample = True
         elif a == '--repeats':
             repeats = int(args.pop(0))
         elif a == '--parent':
             parents.append(args.pop(0))
         else:
             names.append(a)
-    out = out or os.path.join(ROOT, 'profiles', 'seq_chain_speed.json' if chain else 'seq_batch_speed.json')
+    out = out or os.path.join(ROOT, 'profiles', 'seq_sample_speed.json' if sample else
+                              'seq_chain_speed.json' if chain else 'seq_batch_speed.json')
     recs = json.load(open(out)) if os.path.exists(out) else []
     for name in names or ['7b']:
-        rec = run_chain(name, steps, repeats, parents) if chain else run(name, steps)
+        rec = (run_sample(name, steps, repeats) if sample else
+               run_chain(name, steps, repeats, parents) if chain else run(name, steps))
         recs = [r for r in recs if r['model'] != rec['model']] + [rec]
         print(json.dumps(rec), flush=True)
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
