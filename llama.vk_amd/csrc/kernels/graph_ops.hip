@@ -37,7 +37,13 @@ __device__ __forceinline__ void store_f(const GView & v, int64_t i0, int64_t i1,
 __device__ __forceinline__ int64_t nel(const GView & v) { return v.ne[0] * v.ne[1] * v.ne[2] * v.ne[3]; }
 
 // dup / cpy (ggml.c ggml_compute_forward_dup_*): the k-th element of src in logical
-// (row-major, i0 fastest) order goes to the k-th element of dst; f32 <-> f16 RNE
+// (row-major, i0 fastest) order goes to the k-th element of dst; f32 <-> f16 RNE.
+// That is dup_f32 for any two shapes (its destination counters wrap at the destination's
+// extents, ggml.c:4965-4976) and dup_f16 for equal shapes.  For an f16 source and ANOTHER
+// destination shape the reference wraps the destination counters at the source's extents
+// (ggml.c:4871-4881, 4897-4907), which leaves holes in or writes outside the destination;
+// this kernel deliberately keeps k-th to k-th there, and no test compares that case
+// (tests/test_gpu_ggml_ops.py).
 __global__ void k_g_cpy(GView s, GView d) {
     const int64_t n = nel(d);
     for (int64_t k = blockIdx.x * (int64_t) blockDim.x + threadIdx.x; k < n; k += (int64_t) gridDim.x * blockDim.x) {

@@ -317,7 +317,13 @@ hipError_t launch_matvec_q41(const MvLaunch & L, int pro, int epi, hipStream_t s
         return N > 1 ? go41<512, 2, PRO_NORM, EPI_SWIGLU, 2>(P, ng, N, s)
                      : go41<512, 1, PRO_NORM, EPI_SWIGLU, 2>(P, ng, N, s);
     }
-    if (ng % 2) return hipErrorInvalidValue;
+    if (ng % 2) {
+        // an odd number of 8-row groups: one group (wave) per workgroup.  Only the plain
+        // store of float activations has such matrices (ggml_graph_compute's Q4_1 mul_mat
+        // with ne01 % 16 == 8); the model's own matrices have even group counts
+        if (pro != PRO_ACTF || epi != EPI_STORE) return hipErrorInvalidValue;
+        return N > 1 ? go41<64, 2, PRO_ACTF, EPI_STORE, 2>(P, ng, N, s) : go41<64, 1, PRO_ACTF, EPI_STORE, 4>(P, ng, N, s);
+    }
     return N > 1 ? dispatch41<128, 2, 2>(P, pro, epi, ng, N, s) : dispatch41<128, 1, 4>(P, pro, epi, ng, N, s);
 }
 
