@@ -91,6 +91,38 @@ LVK_API int lvk_attention_prompt(const uint16_t * kc, const uint16_t * vc, const
 LVK_API int lvk_attention_decode(const uint16_t * kc, const uint16_t * vc, const float * q, int n_embd, int n_head,
                                  int n_ctx, int n_past, float * out);
 
+/* lvk_attention (kind 0), lvk_attention_prompt (kind 1) or lvk_attention_decode (kind 2, n = 1)
+ * with the kernel's fused Wo quantizer exposed: type 2 (Q4_0) or 3 (Q4_1) selects the quantizer,
+ * blocks (optional) receives the quantized Wo input, n rows of n_embd/32 blocks in the reference
+ * block layout (20 / 24 bytes), i.e. quantize_row_q of each out row.  kinds 1 and 2 keep the shape
+ * limits of their functions; every kind needs head_dim 128, n >= 1, 0 <= n_past <= n_ctx - n. */
+LVK_API int lvk_attention_q(int kind, int type, const uint16_t * kc, const uint16_t * vc, const float * q, int n_embd,
+                            int n_head, int n_ctx, int n_past, int n, float * out, void * blocks);
+
+/* The two kernels of a batched decode layer (attention_rows.hip) on host data.  A cache argument
+ * is a host array [n_slots][n_layer][n_ctx * n_embd] of f16 bits (K [n_ctx][n_embd], V
+ * [n_embd][n_ctx] per slot and layer); slot s is handed to the kernel as its base and the launch
+ * gets the element offset of `layer`.  Row i belongs to slot slots[i] at position pos[i].  Every
+ * argument is checked on the host before anything is uploaded: a slot outside 0..n_slots-1, a
+ * position outside 0..n_ctx-1, layer outside 0..n_layer-1, n < 1, a shape other than head_dim 128,
+ * n_ctx % 32 == 0, n_ctx >= 128, or a bad type returns -1 with a message and launches nothing.
+ *
+ * lvk_rope_kv_rows: k_rope_kv_rows.  qkv [n][3 * n_embd] f32 (stored Q|K|V rows).  Row i is RoPE'd
+ * at pos[i] (the table a context builds); its K and V are written at pos[i] of slot slots[i],
+ * layer `layer`.  kc and vc are read and written in place (whole arrays, up and back).  q16_out is
+ * [n][n_embd] f16 bits.
+ *
+ * lvk_attention_rows: k_attn_rows<type>, type 2 (Q4_0) or 3 (Q4_1).  q [n][n_embd] f32 post-RoPE,
+ * converted to f16 on the host as lvk_attention does.  Row i attends over pos[i] + 1 positions of
+ * slot slots[i], layer `layer`, nothing masked.  out is [n][n_embd] f32; blocks (optional): the
+ * quantized Wo input, n rows of n_embd/32 blocks in the reference block layout (20 / 24 bytes). */
+LVK_API int lvk_rope_kv_rows(const float * qkv, const int * slots, const int * pos, int n, int n_embd, int n_head,
+                             int n_ctx, int n_slots, int n_layer, int layer, uint16_t * kc, uint16_t * vc,
+                             uint16_t * q16_out);
+LVK_API int lvk_attention_rows(int type, const uint16_t * kc, const uint16_t * vc, int n_slots, int n_layer, int layer,
+                               const float * q, const int * slots, const int * pos, int n, int n_embd, int n_head,
+                               int n_ctx, float * out, void * blocks);
+
 /* Self-check of the softmax exp: the number of arguments h <= 0 (fp16 bits)
  * where the device's computed fp16(exp(h)) differs from this host's
  * table_exp_f16[h] (ggml.c:2915-2927) -- 0 when the device expf reproduces it,

@@ -44,6 +44,17 @@ void host_fp16_tables(std::vector<uint16_t> & te, std::vector<uint16_t> & ts) {
     }
 }
 
+// RoPE cos/sin table (ggml.c:7209-7213): theta = powf(10000, -i0/n_dims), angle = p*theta
+void host_rope_table(std::vector<float2> & rt, size_t n_ctx, size_t hd) {
+    rt.resize(n_ctx * (hd / 2));
+    for (size_t pos = 0; pos < n_ctx; ++pos)
+        for (size_t i0 = 0; i0 < hd; i0 += 2) {
+            const float theta = powf(10000.0f, ((float) -(int) i0) / (float) hd);
+            const float ang = (float) (int) pos * theta;
+            rt[pos * (hd / 2) + i0 / 2] = make_float2(cosf(ang), sinf(ang));
+        }
+}
+
 // the softmax may compute exp instead of reading the table, but only in a mode
 // that reproduces this host's table on every argument it can see: 2 (device
 // expf) if exact, else 1 (double exp) if exact, else 0 (table).  LVK_EXP_TABLE
@@ -190,14 +201,8 @@ void Context::init(const llama_context_params & p) {
     LVK_HIP(hipMemcpy(exp_tab, te.data(), 65536 * 2, hipMemcpyHostToDevice));
     LVK_HIP(hipMemcpy(silu_tab, ts.data(), 65536 * 2, hipMemcpyHostToDevice));
     exp_computed = pick_exp_mode(exp_tab);
-    // RoPE cos/sin table (ggml.c:7209-7213): theta = powf(10000, -i0/n_dims), angle = p*theta
-    std::vector<float2> rt(C * (hd / 2));
-    for (size_t pos = 0; pos < C; ++pos)
-        for (size_t i0 = 0; i0 < hd; i0 += 2) {
-            const float theta = powf(10000.0f, ((float) -(int) i0) / (float) hd);
-            const float ang = (float) (int) pos * theta;
-            rt[pos * (hd / 2) + i0 / 2] = make_float2(cosf(ang), sinf(ang));
-        }
+    std::vector<float2> rt;
+    host_rope_table(rt, C, hd);
     rope = (float2 *) model.alloc(rt.size() * sizeof(float2));
     LVK_HIP(hipMemcpy(rope, rt.data(), rt.size() * sizeof(float2), hipMemcpyHostToDevice));
 

@@ -279,6 +279,8 @@ int sample_from_candidates(const SampleOut & so, int k, float top_p, std::mt1993
 int pick_exp_mode(const uint16_t * exp_tab_d);
 // fp16 exp / silu tables (ggml.c:2915-2927) built with this host's glibc expf
 void host_fp16_tables(std::vector<uint16_t> & exp_tab, std::vector<uint16_t> & silu_tab);
+// RoPE {cos, sin} table [n_ctx][hd/2] (ggml.c:7209-7213) built with this host's glibc powf / cosf / sinf
+void host_rope_table(std::vector<float2> & rt, size_t n_ctx, size_t hd);
 
 }  // namespace lvk
 

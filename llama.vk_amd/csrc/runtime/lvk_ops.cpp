@@ -39,6 +39,32 @@ size_t block_bytes(int type) { return type == lvk::Q4_0 ? 20 : 24; }
 
 __attribute__((target("f16c"))) uint16_t h_f32_to_f16(float f) { return _cvtss_sh(f, 0); }
 
+// device arrays of a quantized activation: n rows of nb blocks
+lvk::ActQ actq_alloc(Dev & dv, size_t n, size_t nb) {
+    lvk::ActQ q;
+    q.nb = (int) nb;
+    q.d = (float *) dv.get(n * nb * 4);
+    q.m = (float *) dv.get(n * nb * 4);
+    q.qs = (uint4 *) dv.get(n * nb * 16);
+    return q;
+}
+
+// the first n_blocks blocks of a device ActQ (d, m, qs) as reference blocks (20 / 24 bytes) in host memory
+void pack_blocks(int type, const lvk::ActQ & q, size_t n_blocks, void * y) {
+    std::vector<float> d(n_blocks), m(n_blocks);
+    std::vector<uint8_t> qs(n_blocks * 16);
+    LVK_HIP(hipMemcpy(d.data(), q.d, d.size() * 4, hipMemcpyDeviceToHost));
+    LVK_HIP(hipMemcpy(m.data(), q.m, m.size() * 4, hipMemcpyDeviceToHost));
+    LVK_HIP(hipMemcpy(qs.data(), q.qs, qs.size(), hipMemcpyDeviceToHost));
+    uint8_t * out = (uint8_t *) y;
+    const size_t bb = block_bytes(type);
+    for (size_t i = 0; i < n_blocks; ++i) {
+        std::memcpy(out + i * bb, &d[i], 4);
+        if (type == lvk::Q4_1) std::memcpy(out + i * bb + 4, &m[i], 4);
+        std::memcpy(out + i * bb + bb - 16, &qs[i * 16], 16);
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -59,24 +85,9 @@ int lvk_quantize_rows(int type, const float * x, int n, int k, void * y) {
         Dev dv;
         const size_t nb = (size_t) k / 32;
         float * xd = dv.up(x, (size_t) n * k);
-        lvk::ActQ q;
-        q.nb = (int) nb;
-        q.d = (float *) dv.get((size_t) n * nb * 4);
-        q.m = (float *) dv.get((size_t) n * nb * 4);
-        q.qs = (uint4 *) dv.get((size_t) n * nb * 16);
+        const lvk::ActQ q = actq_alloc(dv, (size_t) n, nb);
         LVK_HIP(lvk::launch_quantize_act(xd, n, k, type, q, nullptr));
-        std::vector<float> d((size_t) n * nb), m((size_t) n * nb);
-        std::vector<uint8_t> qs((size_t) n * nb * 16);
-        LVK_HIP(hipMemcpy(d.data(), q.d, d.size() * 4, hipMemcpyDeviceToHost));
-        LVK_HIP(hipMemcpy(m.data(), q.m, m.size() * 4, hipMemcpyDeviceToHost));
-        LVK_HIP(hipMemcpy(qs.data(), q.qs, qs.size(), hipMemcpyDeviceToHost));
-        uint8_t * out = (uint8_t *) y;
-        const size_t bb = block_bytes(type);
-        for (size_t i = 0; i < (size_t) n * nb; ++i) {
-            std::memcpy(out + i * bb, &d[i], 4);
-            if (type == lvk::Q4_1) std::memcpy(out + i * bb + 4, &m[i], 4);
-            std::memcpy(out + i * bb + bb - 16, &qs[i * 16], 16);
-        }
+        pack_blocks(type, q, (size_t) n * nb, y);
         return 0;
     } catch (const lvk::Error & e) { return fail(__func__, e.msg); }
 }
@@ -236,7 +247,8 @@ int lvk_attention(const uint16_t * kc, const uint16_t * vc, const float * q, int
 }
 
 static int attention_impl(const uint16_t * kc, const uint16_t * vc, const float * q, int n_embd, int n_head,
-                          int n_ctx, int n_past, int n, float * out, float * scores_out, int kind);
+                          int n_ctx, int n_past, int n, float * out, float * scores_out, int kind,
+                          int type = lvk::Q4_0, void * blocks = nullptr);
 
 int lvk_attention_scores(const uint16_t * kc, const uint16_t * vc, const float * q, int n_embd, int n_head,
                          int n_ctx, int n_past, int n, float * out, float * scores_out) {
@@ -257,8 +269,23 @@ int lvk_attention_decode(const uint16_t * kc, const uint16_t * vc, const float *
     return attention_impl(kc, vc, q, n_embd, n_head, n_ctx, n_past, 1, out, nullptr, 2);
 }
 
+int lvk_attention_q(int kind, int type, const uint16_t * kc, const uint16_t * vc, const float * q, int n_embd,
+                    int n_head, int n_ctx, int n_past, int n, float * out, void * blocks) {
+    if (kind < 0 || kind > 2) return fail(__func__, "kind: 0 lvk_attention, 1 lvk_attention_prompt, 2 lvk_attention_decode");
+    if (type != lvk::Q4_0 && type != lvk::Q4_1) return fail(__func__, "type: 2 (Q4_0) or 3 (Q4_1)");
+    if (!kc || !vc || !q || !out || n_head < 1 || n_embd != n_head * 128 || n < 1 || n_past < 0 || n_ctx < 1 ||
+        n_past > n_ctx - n)
+        return fail(__func__, "need head_dim 128, n >= 1 and 0 <= n_past <= n_ctx - n");
+    if (kind == 1 && !lvk::attention_prompt_supported(n_embd, n_head, n_ctx))
+        return fail(__func__, "kind 1 needs head_dim 128, n_ctx % 32 == 0, n_ctx <= 1024");
+    if (kind == 2 && (n != 1 || !lvk::attention_decode_supported(n_embd, n_head, n_ctx)))
+        return fail(__func__, "kind 2 needs n == 1, head_dim 128, n_ctx % 64 == 0, n_ctx <= 2048");
+    return attention_impl(kc, vc, q, n_embd, n_head, n_ctx, n_past, n, out, nullptr, kind, type, blocks);
+}
+
 static int attention_impl(const uint16_t * kc, const uint16_t * vc, const float * q, int n_embd, int n_head,
-                          int n_ctx, int n_past, int n, float * out, float * scores_out, int kind) {
+                          int n_ctx, int n_past, int n, float * out, float * scores_out, int kind, int type,
+                          void * blocks) {
     const char * fn = kind == 1 ? "lvk_attention_prompt" : kind == 2 ? "lvk_attention_decode" : "lvk_attention";
     try {
         Dev dv;
@@ -271,11 +298,8 @@ static int attention_impl(const uint16_t * kc, const uint16_t * vc, const float 
         A.kc = dv.up(kc, CE);
         A.vc = dv.up(vc, CE);
         A.scores = (float *) dv.get((size_t) n * n_head * n_ctx * 4);
-        A.out.nb = n_embd / 32;
-        A.out.d = (float *) dv.get((size_t) n * n_embd / 32 * 4);
-        A.out.m = (float *) dv.get((size_t) n * n_embd / 32 * 4);
-        A.out.qs = (uint4 *) dv.get((size_t) n * n_embd / 32 * 16);
-        A.out_qtype = lvk::Q4_0;
+        A.out = actq_alloc(dv, (size_t) n, (size_t) n_embd / 32);
+        A.out_qtype = type;
         std::vector<uint16_t> te, ts;
         lvk::host_fp16_tables(te, ts);
         A.exp_tab = dv.up(te.data(), te.size());
@@ -295,6 +319,7 @@ static int attention_impl(const uint16_t * kc, const uint16_t * vc, const float 
         }
         else LVK_HIP(lvk::launch_attention(A, nullptr));
         LVK_HIP(hipMemcpy(out, od, (size_t) n * n_embd * 4, hipMemcpyDeviceToHost));
+        if (blocks) pack_blocks(type, A.out, (size_t) n * A.out.nb, blocks);
         if (scores_out) {
             LVK_HIP(hipMemcpy(scores_out, A.scores, (size_t) n * n_head * n_ctx * 4, hipMemcpyDeviceToHost));
             // the f16 probabilities follow the scores (lvk_ops.h: scores_out holds 1.5x the floats)
@@ -303,6 +328,102 @@ static int attention_impl(const uint16_t * kc, const uint16_t * vc, const float 
         }
         return 0;
     } catch (const lvk::Error & e) { return fail(fn, e.msg); }
+}
+
+// ---- the batched-decode rows kernels (attention_rows.hip) on host data
+namespace {
+
+// the host-side checks of both rows entry points: nothing out of range reaches a kernel
+const char * rows_args_bad(const int * slots, const int * pos, int n, int n_embd, int n_head, int n_ctx, int n_slots,
+                           int n_layer, int layer) {
+    if (!slots || !pos) return "null argument";
+    if (n < 1) return "n must be >= 1";
+    if (n_slots < 1 || n_layer < 1) return "n_slots and n_layer must be >= 1";
+    if (layer < 0 || layer >= n_layer) return "layer outside 0..n_layer-1";
+    if (!lvk::attention_rows_supported(n_embd, n_head, n_ctx)) return "needs head_dim 128, n_ctx % 32 == 0, n_ctx >= 128";
+    for (int i = 0; i < n; ++i) {
+        if (slots[i] < 0 || slots[i] >= n_slots) return "a slot outside 0..n_slots-1";
+        if (pos[i] < 0 || pos[i] >= n_ctx) return "a position outside 0..n_ctx-1";
+    }
+    return nullptr;
+}
+
+// host caches [n_slots][n_layer][n_ctx * n_embd] -> device copies, the slot table and the row table
+struct RowsDev {
+    uint16_t * kc, * vc;
+    lvk::SeqSlot * slots;
+    lvk::SeqRow * rows;
+    size_t layer_off, total;
+};
+RowsDev rows_upload(Dev & dv, const uint16_t * kc, const uint16_t * vc, const int * slots, const int * pos, int n,
+                    int n_embd, int n_ctx, int n_slots, int n_layer, int layer) {
+    const size_t CE = (size_t) n_ctx * n_embd;
+    RowsDev r;
+    r.total = (size_t) n_slots * n_layer * CE;
+    r.layer_off = (size_t) layer * CE;
+    r.kc = dv.up(kc, r.total);
+    r.vc = dv.up(vc, r.total);
+    std::vector<lvk::SeqSlot> st((size_t) n_slots);
+    for (int s = 0; s < n_slots; ++s) st[(size_t) s] = {r.kc + (size_t) s * n_layer * CE, r.vc + (size_t) s * n_layer * CE};
+    std::vector<lvk::SeqRow> rw((size_t) n);
+    for (int i = 0; i < n; ++i) rw[(size_t) i] = {slots[i], pos[i]};
+    r.slots = dv.up(st.data(), st.size());
+    r.rows = dv.up(rw.data(), rw.size());
+    return r;
+}
+
+}  // namespace
+
+int lvk_rope_kv_rows(const float * qkv, const int * slots, const int * pos, int n, int n_embd, int n_head, int n_ctx,
+                     int n_slots, int n_layer, int layer, uint16_t * kc, uint16_t * vc, uint16_t * q16_out) {
+    try {
+        if (!qkv || !kc || !vc || !q16_out) return fail(__func__, "null argument");
+        if (const char * bad = rows_args_bad(slots, pos, n, n_embd, n_head, n_ctx, n_slots, n_layer, layer))
+            return fail(__func__, bad);
+        Dev dv;
+        const int hd = n_embd / n_head;
+        const RowsDev r = rows_upload(dv, kc, vc, slots, pos, n, n_embd, n_ctx, n_slots, n_layer, layer);
+        std::vector<float2> rt;
+        lvk::host_rope_table(rt, (size_t) n_ctx, (size_t) hd);
+        const float2 * rope = dv.up(rt.data(), rt.size());
+        const float * qd = dv.up(qkv, (size_t) n * 3 * n_embd);
+        uint16_t * q16 = (uint16_t *) dv.get((size_t) n * n_embd * 2);
+        LVK_HIP(lvk::launch_rope_kv_rows(qd, n, n_embd, hd, rope, r.rows, r.slots, r.layer_off, n_ctx, q16, nullptr));
+        LVK_HIP(hipMemcpy(q16_out, q16, (size_t) n * n_embd * 2, hipMemcpyDeviceToHost));
+        LVK_HIP(hipMemcpy(kc, r.kc, r.total * 2, hipMemcpyDeviceToHost));
+        LVK_HIP(hipMemcpy(vc, r.vc, r.total * 2, hipMemcpyDeviceToHost));
+        return 0;
+    } catch (const lvk::Error & e) { return fail(__func__, e.msg); }
+}
+
+int lvk_attention_rows(int type, const uint16_t * kc, const uint16_t * vc, int n_slots, int n_layer, int layer,
+                       const float * q, const int * slots, const int * pos, int n, int n_embd, int n_head, int n_ctx,
+                       float * out, void * blocks) {
+    try {
+        if (!kc || !vc || !q || !out) return fail(__func__, "null argument");
+        if (type != lvk::Q4_0 && type != lvk::Q4_1) return fail(__func__, "type: 2 (Q4_0) or 3 (Q4_1)");
+        if (const char * bad = rows_args_bad(slots, pos, n, n_embd, n_head, n_ctx, n_slots, n_layer, layer))
+            return fail(__func__, bad);
+        Dev dv;
+        const RowsDev r = rows_upload(dv, kc, vc, slots, pos, n, n_embd, n_ctx, n_slots, n_layer, layer);
+        std::vector<uint16_t> q16((size_t) n * n_embd);
+        for (size_t i = 0; i < q16.size(); ++i) q16[i] = h_f32_to_f16(q[i]);   // ggml.c:6420-6433
+        lvk::AttnLaunch A{};
+        A.q16 = dv.up(q16.data(), q16.size());
+        A.out = actq_alloc(dv, (size_t) n, (size_t) n_embd / 32);
+        A.out_qtype = type;
+        std::vector<uint16_t> te, ts;
+        lvk::host_fp16_tables(te, ts);
+        A.exp_tab = dv.up(te.data(), te.size());
+        A.exp_computed = lvk::pick_exp_mode(A.exp_tab);
+        A.n_tokens = n; A.n_embd = n_embd; A.n_head = n_head; A.n_ctx = n_ctx;
+        float * od = (float *) dv.get((size_t) n * n_embd * 4);
+        A.out_f32 = od;
+        LVK_HIP(lvk::launch_attention_rows(A, r.rows, r.slots, r.layer_off, nullptr));
+        LVK_HIP(hipMemcpy(out, od, (size_t) n * n_embd * 4, hipMemcpyDeviceToHost));
+        if (blocks) pack_blocks(type, A.out, (size_t) n * A.out.nb, blocks);
+        return 0;
+    } catch (const lvk::Error & e) { return fail(__func__, e.msg); }
 }
 
 int lvk_exp_table_mismatches(void) {

@@ -115,6 +115,11 @@ _sig("lvk_attention", C.c_int, [u16p, u16p, f32p, C.c_int, C.c_int, C.c_int, C.c
 _sig("lvk_attention_prompt", C.c_int, [u16p, u16p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p])
 _sig("lvk_attention_decode", C.c_int, [u16p, u16p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, f32p])
 _sig("lvk_attention_scores", C.c_int, [u16p, u16p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, f32p])
+_sig("lvk_attention_q", C.c_int, [C.c_int, C.c_int, u16p, u16p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, u8p])
+_sig("lvk_rope_kv_rows", C.c_int, [f32p, i32p, i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                   u16p, u16p, u16p])
+_sig("lvk_attention_rows", C.c_int, [C.c_int, u16p, u16p, C.c_int, C.c_int, C.c_int, f32p, i32p, i32p, C.c_int, C.c_int,
+                                     C.c_int, C.c_int, f32p, u8p])
 _sig("lvk_rms_norm_mul", C.c_int, [f32p, f32p, C.c_int, C.c_int, f32p])
 _sig("lvk_exp_table_mismatches", C.c_int, [])
 _sig("lvk_host_tables", None, [u16p, u16p])
@@ -605,6 +610,61 @@ def attention_scores(kc, vc, q, n_embd, n_head, n_ctx, n_past, n):
                                     out, sc), "lvk_attention_scores")
     p16 = sc[m:].view(np.uint16)[:m].reshape(n, n_head, n_ctx)
     return out, sc[:m].reshape(n, n_head, n_ctx), p16
+
+
+def attention_q(kind, qtype, kc, vc, q, n_embd, n_head, n_ctx, n_past, n):
+    """lvk_attention_q: kind 0 / 1 / 2 = attention / attention_prompt / attention_decode with the fused Wo
+    quantizer of type qtype; returns (out [n][n_embd] f32, blocks [n][n_embd/32 * block bytes] uint8)"""
+    out = np.zeros(n * n_embd, np.float32)
+    blocks = np.zeros(n * (n_embd // 32) * BLOCK_BYTES.get(qtype, 24), np.uint8)
+    _check(lib.lvk_attention_q(kind, qtype, np.ascontiguousarray(kc, np.uint16).ravel(),
+                               np.ascontiguousarray(vc, np.uint16).ravel(), np.ascontiguousarray(q, np.float32).ravel(),
+                               n_embd, n_head, n_ctx, n_past, n, out, blocks), "lvk_attention_q")
+    return out.reshape(n, n_embd), blocks.reshape(n, -1)
+
+
+def _rows_caches(kc, vc, n_ctx, n_embd):
+    """caches [n_slots][n_layer][n_ctx * n_embd] of f16 bits -> (kc, vc, n_slots, n_layer)"""
+    kc, vc = np.ascontiguousarray(kc, np.uint16), np.ascontiguousarray(vc, np.uint16)
+    if kc.ndim != 3 or kc.shape != vc.shape or kc.shape[2] != n_ctx * n_embd:
+        raise ValueError("caches must be [n_slots][n_layer][n_ctx * n_embd]")
+    return kc, vc, kc.shape[0], kc.shape[1]
+
+
+def rope_kv_rows(qkv, slots, pos, n_embd, n_head, n_ctx, layer, kc, vc):
+    """lvk_rope_kv_rows (k_rope_kv_rows): qkv [n][3 * n_embd]; kc / vc [n_slots][n_layer][n_ctx * n_embd] uint16.
+    Returns (q16 [n][n_embd] uint16, kc, vc): the caches after the launch (the arguments are not changed)"""
+    kc, vc, n_slots, n_layer = _rows_caches(kc, vc, n_ctx, n_embd)
+    kc, vc = kc.copy(), vc.copy()
+    slots, pos = np.ascontiguousarray(slots, np.int32), np.ascontiguousarray(pos, np.int32)
+    n = len(slots)
+    if len(pos) != n:
+        raise ValueError("slots and pos differ in length")
+    qkv = np.ascontiguousarray(qkv, np.float32).ravel()
+    if qkv.size != n * 3 * n_embd:
+        raise ValueError("qkv must be [n][3 * n_embd]")
+    q16 = np.zeros(n * n_embd, np.uint16)
+    _check(lib.lvk_rope_kv_rows(qkv, slots, pos, n, n_embd, n_head, n_ctx, n_slots, n_layer, layer,
+                                kc.ravel(), vc.ravel(), q16), "lvk_rope_kv_rows")
+    return q16.reshape(n, n_embd), kc, vc
+
+
+def attention_rows(qtype, kc, vc, layer, q, slots, pos, n_embd, n_head, n_ctx):
+    """lvk_attention_rows (k_attn_rows): kc / vc [n_slots][n_layer][n_ctx * n_embd] uint16, q [n][n_embd] f32.
+    Returns (out [n][n_embd] f32, blocks [n][n_embd/32 * block bytes] uint8)"""
+    kc, vc, n_slots, n_layer = _rows_caches(kc, vc, n_ctx, n_embd)
+    slots, pos = np.ascontiguousarray(slots, np.int32), np.ascontiguousarray(pos, np.int32)
+    n = len(slots)
+    if len(pos) != n:
+        raise ValueError("slots and pos differ in length")
+    q = np.ascontiguousarray(q, np.float32).ravel()
+    if q.size != n * n_embd:
+        raise ValueError("q must be [n][n_embd]")
+    out = np.zeros(n * n_embd, np.float32)
+    blocks = np.zeros(n * (n_embd // 32) * BLOCK_BYTES.get(qtype, 24), np.uint8)
+    _check(lib.lvk_attention_rows(qtype, kc.ravel(), vc.ravel(), n_slots, n_layer, layer, q, slots, pos, n, n_embd,
+                                  n_head, n_ctx, out, blocks), "lvk_attention_rows")
+    return out.reshape(n, n_embd), blocks.reshape(n, -1)
 
 
 def exp_table_mismatches():

@@ -201,6 +201,41 @@ def test_7b_shaped_rows(lvk, model_dir, ftype, n_big):
     m.close()
 
 
+@pytest.mark.parametrize("ftype", [2, 3])
+def test_rows_past_512_positions_match_the_oracle(lvk, oracle, model_dir, ftype):
+    """n_ctx = 1024 and slots of 500 .. 600 positions, one row each in one call: n_kv = pos + 1 of
+    501, 512, 513, 531, 544, 545 and 601 runs the rows attention's second K block, its V steps
+    from global memory and its double tail from LDS and from global memory, with the context's slot
+    table, layer_off of the second layer at this n_ctx and lvk_seq_copy past 512 positions.  The
+    slots are copies of one 600-token prefix evaluated through the prompt path; every logits row
+    is compared with the oracle model, which evaluates the prefix once and then the single tokens
+    longest slot first (as in test_7b_shaped_rows: an eval at n_past = m writes position m, which
+    the evals of the shorter slots after it never read)."""
+    from oracle_lib import forced_tokens, gen_model
+    path = gen_model(os.path.join(model_dir, "w256_l2_t%d.bin" % ftype), n_embd=256, n_head=2, n_layer=2, ftype=ftype,
+                     seed=40 + ftype)
+    n_ctx, n_pre = 1024, 600
+    lens = [500, 511, 512, 530, 543, 544, 600]
+    pre = forced_tokens(n_pre, seed=41)
+    tok = forced_tokens(len(lens), seed=42)
+    om = oracle.model(path, n_ctx)
+    om.eval(pre, 0)
+    want = [None] * len(lens)
+    for i in reversed(range(len(lens))):
+        want[i] = om.eval([int(tok[i])], lens[i])
+    om.close()
+    m = lvk.Llama(path, n_ctx=n_ctx)
+    m.seq_init(len(lens) + 1)
+    m.eval(pre, 0)
+    for i, n in enumerate(lens):
+        m.seq_copy(1 + i, 0, n)
+    assert [m.seq_tokens(1 + i) for i in range(len(lens))] == lens
+    lg, am = m.decode_batch(tok, [1 + i for i in range(len(lens))], lens, argmax=True)
+    check_rows(lg, am, want, "ftype %d" % ftype)
+    assert [m.seq_tokens(1 + i) for i in range(len(lens))] == [n + 1 for n in lens]
+    m.close()
+
+
 def test_batch_errors(lvk, models):
     """argument checks: every bad call raises, changes no slot's count and leaves the context
     usable; contexts that cannot hold slots refuse seq_init and still evaluate"""
