@@ -91,6 +91,12 @@ LVK_API int lvk_attention_prompt(const uint16_t * kc, const uint16_t * vc, const
 LVK_API int lvk_attention_decode(const uint16_t * kc, const uint16_t * vc, const float * q, int n_embd, int n_head,
                                  int n_ctx, int n_past, float * out);
 
+/* Score-helper workgroups per head that a decode-attention launch of this shape runs on the
+ * current device (attention_decode.hip): 4 when n_head * 8 <= compute units, else 0; 0 as well
+ * with env LVK_ATTN_HELPERS=0 (read once per process) or for a shape the decode kernels do
+ * not take. */
+LVK_API int lvk_attn_helpers_active(int n_embd, int n_head, int n_ctx);
+
 /* lvk_attention (kind 0), lvk_attention_prompt (kind 1) or lvk_attention_decode (kind 2, n = 1)
  * with the kernel's fused Wo quantizer exposed: type 2 (Q4_0) or 3 (Q4_1) selects the quantizer,
  * blocks (optional) receives the quantized Wo input, n rows of n_embd/32 blocks in the reference

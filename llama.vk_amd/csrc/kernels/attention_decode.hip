@@ -19,8 +19,9 @@
 //      format (quantize_row_q4_0 / _q4_1, ggml.c:621-685 / 847-920).
 //
 // Every workgroup of a launch is resident at once (4 H <= 1024 workgroups of
-// <= 42 KB LDS), which the exchange needs; every spin is bounded so a violated
-// assumption cannot hang the GPU.
+// <= 42 KB LDS; with score helpers 8 H <= CUs workgroups, one per CU), which
+// the exchange needs; every spin is bounded so a violated assumption cannot
+// hang the GPU.
 #include "attention_common.h"
 #include "lvk_kernels.h"
 #include "matvec_common.h"
@@ -68,7 +69,7 @@ __device__ unsigned long long g_dtrace[32 * 4 * 4 * 16];
 #define LVK_DT(ev)                                                                                        \
     do {                                                                                                  \
         const unsigned long long t_ = __builtin_amdgcn_s_memtime();                                       \
-        if ((tid & 63) == 0 && h < 32) g_dtrace[((h * 4 + sl) * 4 + (tid >> 6)) * 16 + (ev)] = t_; \
+        if ((tid & 63) == 0 && h < 32 && sl < 4) g_dtrace[((h * 4 + sl) * 4 + (tid >> 6)) * 16 + (ev)] = t_; \
     } while (0)
 #else
 #define LVK_DT(ev) do { } while (0)
@@ -89,12 +90,20 @@ struct AttnDArgs {
     unsigned * err;               // host-mapped error word (nullptr: none)
     int short_max;                // n_kv <= short_max: no score exchange (every workgroup scores all)
     int seq_epochs;               // epoch += sp->seq << 7 (granules never zeroed between tokens)
+    int nh;                       // score-helper workgroups per head (grid.y = 4 + nh): 0 or 4
 };
 
 // The 4 workgroups (h, sl) of a head either split the scores and exchange them as granules, or
 // (n_kv <= A.short_max) every workgroup scores all positions itself (4x the K reads, from the
 // XCD's L2).  EM: the exp mode compiled in (lvk_device.h exp_softmax) -- a runtime mode puts
 // the table path's load, and its vmcnt wait, into the softmax loop.
+//
+// Score helpers (A.nh = 4, launch_attention_decode): workgroups (h, 4 .. 7) own no V slice.  In
+// the exchange schedule the head's 64-position chunks are dealt over all 8 workgroups (workgroup
+// sl scores chunks sl, sl + 8, ...), so the K bytes each of the 4 slice workgroups pulls through
+// its CU ahead of the softmax are halved; a helper publishes its granules like everyone else
+// and returns before the first barrier, without a V DMA or an LDS access.  Nobody waits for a
+// helper except through the granules every consumer polls anyway (bounded).
 template <int QT, int EM>
 __global__ __launch_bounds__(256) void k_attn_d(AttnDArgs A) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -150,8 +159,10 @@ __global__ __launch_bounds__(256) void k_attn_d(AttnDArgs A) {
     const int n_pad = (n_kv + 31) & ~31;
     const int np = n_kv & ~31;
     const bool exch = n_kv > A.short_max;
-    const int cs = exch ? 256 : 64;                     // position stride of this workgroup's chunks
+    const int cs = exch ? (4 + A.nh) * 64 : 64;         // position stride of this workgroup's chunks
     const int cb = exch ? sl * 64 : 0;                  // its first chunk
+    const bool helper = sl >= 4;                        // workgroup-uniform
+    if (helper && (!exch || cb >= n_kv)) return;        // nothing to score
     // this workgroup's first two K chunks, issued once n_past is known.  (A speculative load
     // of positions 0..63 before the step block, which only the short schedule and workgroup 0
     // use, measured 0.1-0.25 us slower per launch: it queued ahead of the chunks an exchange
@@ -197,7 +208,8 @@ __global__ __launch_bounds__(256) void k_attn_d(AttnDArgs A) {
         // own K rows, the V rows are needed after the softmax.  (Chunk 0 of V issued with Q
         // and K chunk 0, or right after the n_past-dependent K loads: 5.66-5.73 / 5.71-5.77 us
         // against 5.42-5.47 us per launch here, 7B decode_speed, profiles/r04_attn_vorder.jsonl)
-        for (int p0 = 0; p0 < n_pad; p0 += 512) v_dma(p0, 0, n_pad);
+        if (!helper)
+            for (int p0 = 0; p0 < n_pad; p0 += 512) v_dma(p0, 0, n_pad);
         LVK_DT(7);
         LVK_DT(1);
         for (int c0 = cb + 2 * cs; c0 < n_kv; c0 += cs) {
@@ -209,6 +221,7 @@ __global__ __launch_bounds__(256) void k_attn_d(AttnDArgs A) {
             score(k4, p);
         }
     }
+    if (helper) return;         // its granules are out: no barrier, no LDS access before this
     LVK_DT(2);
     // 2. softmax (ggml.c:7099-7121; no position is masked in a decode step).  Exchange: the
     // granules are read four at a time; the ones without this layer's epoch are polled.
@@ -346,6 +359,15 @@ __global__ __launch_bounds__(256) void k_attn_d(AttnDArgs A) {
 // LDS of one decode-attention workgroup (V slice, scores, probabilities, reductions)
 __host__ __device__ inline size_t attn_lds(int n_ctx) { return (size_t) 32 * (n_ctx + 32) * 2 + (size_t) n_ctx * 6 + 80; }
 
+// score-helper workgroups per head: 4 when all 8 workgroups of every head get a CU of their own
+// (7B: 256 workgroups on 256 CUs), else 0 -- a second workgroup on a CU would share that CU's
+// ingest with the slice workgroup it is meant to relieve.  LVK_ATTN_HELPERS=0 turns them off
+// (read once per process; A/B runs and tests/test_gpu_attn_helpers.py).
+inline int attn_helpers(int n_head) {
+    static const bool on = [] { const char * e = getenv("LVK_ATTN_HELPERS"); return !e || atoi(e) != 0; }();
+    return on && n_head * 8 <= cu_count() ? 4 : 0;
+}
+
 // kernel arguments of a decode-attention launch (host side)
 inline AttnDArgs attn_args(const AttnLaunch & A, void * gran, unsigned epoch) {
     AttnDArgs a{};
@@ -371,6 +393,7 @@ inline AttnDArgs attn_args(const AttnLaunch & A, void * gran, unsigned epoch) {
     }();
     a.short_max = short_max;
     a.seq_epochs = A.seq_epochs;
+    a.nh = attn_helpers(A.n_head);
     return a;
 }
 
@@ -384,6 +407,10 @@ bool attention_decode_supported(int n_embd, int n_head, int n_ctx) {
     return n_embd / n_head == HD && n_ctx % 64 == 0 && n_ctx <= 2048 && n_head * 4 <= 1024;
 }
 
+int attention_decode_helpers(int n_embd, int n_head, int n_ctx) {
+    return attention_decode_supported(n_embd, n_head, n_ctx) ? attn_helpers(n_head) : 0;
+}
+
 size_t attention_decode_scratch_bytes(int n_head, int n_ctx) {
     // score granules [H][n_ctx]
     return (size_t) n_head * n_ctx * 8;
@@ -395,7 +422,9 @@ hipError_t launch_attention_decode(const AttnLaunch & A, void * gran, unsigned e
     if (A.out_qtype != Q4_0 && A.out_qtype != Q4_1) return hipErrorNotSupported;
     const AttnDArgs a = attn_args(A, gran, epoch);
     const size_t lds = attn_lds(A.n_ctx);
-    const dim3 grid(A.n_head, HD / 32);
+    // (one LDS size per launch: a helper workgroup is allocated the slice workgroups' LDS and
+    // leaves it untouched; 8 H such workgroups are resident at once because each has its own CU)
+    const dim3 grid(A.n_head, HD / 32 + a.nh);
     with_exp_mode(A.exp_computed, [&](auto em) {
         if (A.out_qtype == Q4_1) LVK_LAUNCH((k_attn_d<Q4_1, em()>), grid, dim3(256), lds, s, a);
         else LVK_LAUNCH((k_attn_d<Q4_0, em()>), grid, dim3(256), lds, s, a);

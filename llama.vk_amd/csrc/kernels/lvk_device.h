@@ -105,6 +105,12 @@ __device__ __forceinline__ uint4 ld_nt(const uint4 * p) {
     const u32x4 v = __builtin_nontemporal_load((const u32x4 *) p);
     return make_uint4(v.x, v.y, v.z, v.w);
 }
+// (the per-chunk scale / min images of the quantized weights are streamed once as well)
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float4 ld_nt(const float4 * p) {
+    const f32x4 v = __builtin_nontemporal_load((const f32x4 *) p);
+    return make_float4(v.x, v.y, v.z, v.w);
+}
 
 __device__ __forceinline__ double warp_sum_d(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);

@@ -192,6 +192,8 @@ hipError_t exp_check(const uint16_t * exp_tab, int * bad_d, hipStream_t s);
 // A.seq_epochs is set (else the scratch must be zeroed before every token).  Needs
 // A.n_tokens == 1.
 bool attention_decode_supported(int n_embd, int n_head, int n_ctx);
+// score-helper workgroups per head of such a launch on the current device (0 or 4)
+int attention_decode_helpers(int n_embd, int n_head, int n_ctx);
 size_t attention_decode_scratch_bytes(int n_head, int n_ctx);
 hipError_t launch_attention_decode(const AttnLaunch & A, void * gran, unsigned epoch, hipStream_t s);
 

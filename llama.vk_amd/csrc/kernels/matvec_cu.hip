@@ -197,11 +197,15 @@ __device__ __forceinline__ void mv_cu_run(const CuParams & P, const int bid, con
     uint4 W[D][4];
     float4 S[D];
     // the scales of a chunk go out before its nibbles: the scale table of chunk c+1 is
-    // built while chunk c's nibbles may still be in flight (vmcnt retires in order)
+    // built while chunk c's nibbles may still be in flight (vmcnt retires in order).  Scales
+    // and nibbles are both read once per token: nt loads, all of them (a plain scale load is
+    // also free to sink behind the chunk's nt nibble loads, which hipcc did; with plain
+    // scales in the Wo matvec alone the next attention launch measured 0.15-0.3 us slower,
+    // profiles/nt_helpers_decode_speed.json)
 #define LVK_ISSUE(slot, grp, cc)                                                                        \
     do {                                                                                                \
         const uint4 * nb_ = P.nib + ((size_t) (grp) * NC * 4 + (cc) * 4) * 64;                          \
-        S[slot] = *(const float4 *) ((const char *) (P.scl + ((size_t) (grp) * NC + (cc)) * 64) + loff); \
+        S[slot] = ld_nt((const float4 *) ((const char *) (P.scl + ((size_t) (grp) * NC + (cc)) * 64) + loff)); \
         _Pragma("unroll") for (int sb = 0; sb < 4; ++sb) if ((cc) * 4 + sb < nsub)                      \
             W[slot][sb] = ld_nt((const uint4 *) ((const char *) (nb_ + sb * 64) + loff));               \
         __builtin_amdgcn_sched_barrier(0);                                                              \

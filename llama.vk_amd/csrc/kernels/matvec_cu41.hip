@@ -121,8 +121,8 @@ __global__ __launch_bounds__(NW * 64) void k_mv_cu41(Cu41Params P) {
         _Pragma("unroll") for (int sb = 0; sb < 4; ++sb) if ((cc) * 4 + sb < nsub)                      \
             W[slot][sb] = ld_nt((const uint4 *) ((const char *) P.nib + (BN) + ((cc) * 4 + sb) * 1024)); \
         const char * sc_ = (const char *) P.scl + (BS) + (cc) * 2048;                                   \
-        SD[slot] = *(const float4 *) sc_;                                                               \
-        SM[slot] = *(const float4 *) (sc_ + 1024);                                                      \
+        SD[slot] = ld_nt((const float4 *) sc_);                                                         \
+        SM[slot] = ld_nt((const float4 *) (sc_ + 1024));                                                \
         WS[slot] = ld_nt((const uint4 *) ((const char *) P.wsum + (BW) + (cc) * 1024));                 \
         __builtin_amdgcn_sched_barrier(0);                                                              \
     } while (0)

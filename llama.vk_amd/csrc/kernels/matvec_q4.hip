@@ -200,7 +200,7 @@ __global__ __launch_bounds__(NT) void k_matvec_q40(Params P) {
                 if (KT == 0) W[slot][sb] = ld_nt(nib + (size_t) min(cl_ * 4 + sb, nsub - 1) * 64);  \
                 else if (cl_ * 4 + sb < nsub) W[slot][sb] = ld_nt(nib + (size_t) (cl_ * 4 + sb) * 64); \
             }                                                                                       \
-            S[slot] = scl[(size_t) cl_ * 64];                                                       \
+            S[slot] = ld_nt(scl + (size_t) cl_ * 64);                                                    \
         }                                                                                           \
     } while (0)
 #pragma unroll

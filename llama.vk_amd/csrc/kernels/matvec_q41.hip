@@ -73,8 +73,8 @@ __global__ __launch_bounds__(NT) void k_matvec_q41(P41 P) {
         const int cl_ = min((cc), NC - 1);                                                         \
         _Pragma("unroll") for (int sb = 0; sb < 4; ++sb)                                           \
             W[slot][sb] = ld_nt(nib + (size_t) min(cl_ * 4 + sb, nsub - 1) * 64);                  \
-        SD[slot] = scl[(size_t) cl_ * 128];                                                        \
-        SM[slot] = scl[(size_t) cl_ * 128 + 64];                                                   \
+        SD[slot] = ld_nt(scl + (size_t) cl_ * 128);                                                \
+        SM[slot] = ld_nt(scl + (size_t) cl_ * 128 + 64);                                           \
     } while (0)
 #pragma unroll
     for (int d = 0; d < D; ++d) LVK_ISSUE41(d, d);

@@ -269,6 +269,11 @@ int lvk_attention_decode(const uint16_t * kc, const uint16_t * vc, const float *
     return attention_impl(kc, vc, q, n_embd, n_head, n_ctx, n_past, 1, out, nullptr, 2);
 }
 
+int lvk_attn_helpers_active(int n_embd, int n_head, int n_ctx) {
+    if (n_embd < 1 || n_head < 1 || n_ctx < 1) return 0;
+    return lvk::attention_decode_helpers(n_embd, n_head, n_ctx);
+}
+
 int lvk_attention_q(int kind, int type, const uint16_t * kc, const uint16_t * vc, const float * q, int n_embd,
                     int n_head, int n_ctx, int n_past, int n, float * out, void * blocks) {
     if (kind < 0 || kind > 2) return fail(__func__, "kind: 0 lvk_attention, 1 lvk_attention_prompt, 2 lvk_attention_decode");

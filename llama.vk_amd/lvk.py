@@ -122,6 +122,7 @@ _sig("lvk_attention_rows", C.c_int, [C.c_int, u16p, u16p, C.c_int, C.c_int, C.c_
                                      C.c_int, C.c_int, f32p, u8p])
 _sig("lvk_rms_norm_mul", C.c_int, [f32p, f32p, C.c_int, C.c_int, f32p])
 _sig("lvk_exp_table_mismatches", C.c_int, [])
+_sig("lvk_attn_helpers_active", C.c_int, [C.c_int, C.c_int, C.c_int])
 _sig("lvk_host_tables", None, [u16p, u16p])
 _sig("lvk_set_profiling", None, [C.c_void_p, C.c_int])
 _sig("lvk_get_profile", C.c_int, [C.c_void_p, f64p, i64p, f64p, C.c_int])
@@ -591,6 +592,11 @@ def attention_decode(kc, vc, q, n_embd, n_head, n_ctx, n_past):
     _check(lib.lvk_attention_decode(kc, vc, np.ascontiguousarray(q, np.float32), n_embd, n_head, n_ctx, n_past, out),
            "lvk_attention_decode")
     return out
+
+
+def attn_helpers_active(n_embd, n_head, n_ctx):
+    """score-helper workgroups per head of a decode-attention launch (lvk_attn_helpers_active)"""
+    return int(lib.lvk_attn_helpers_active(n_embd, n_head, n_ctx))
 
 
 def attention(kc, vc, q, n_embd, n_head, n_ctx, n_past, n):
