@@ -15,25 +15,9 @@
 #include <vector>
 
 #include "../../../include/ggml.h"
-#include "lvk_model.h"
+#include "lvk_buffers.h"
 
 namespace {
-
-struct DevBufs {
-    std::vector<void *> ptrs;
-    void * get(size_t n) {
-        void * p = nullptr;
-        LVK_HIP(hipMalloc(&p, n ? n : 16));
-        ptrs.push_back(p);
-        return p;
-    }
-    template <class T> T * up(const T * h, size_t n) {
-        T * d = (T *) get(n * sizeof(T));
-        LVK_HIP(hipMemcpy(d, h, n * sizeof(T), hipMemcpyHostToDevice));
-        return d;
-    }
-    ~DevBufs() { for (void * p : ptrs) (void) hipFree(p); }
-};
 
 [[noreturn]] void die(const char * fn, const std::string & m) {
     fprintf(stderr, "%s: %s\n", fn, m.c_str());
@@ -56,7 +40,7 @@ void blocks_to_act(int qt, const uint8_t * b, int nb, int nb_pad, std::vector<fl
     }
 }
 
-lvk::ActQ act_up(DevBufs & dv, const std::vector<float> & d, const std::vector<float> & m, const std::vector<uint8_t> & qs) {
+lvk::ActQ act_up(lvk::Scratch & dv, const std::vector<float> & d, const std::vector<float> & m, const std::vector<uint8_t> & qs) {
     lvk::ActQ a;
     a.nb = (int) d.size();
     a.d = dv.up(d.data(), d.size());
@@ -85,7 +69,7 @@ void dequantize_row(const void * x, float * y, int k) {
     try {
         if (k % 32) throw lvk::Error("k must be a multiple of 32");
         if (k == 0) return;
-        DevBufs dv;
+        lvk::Scratch dv;
         const uint8_t * xd = dv.up((const uint8_t *) x, (size_t) k / 32 * block_bytes(QT));
         const int tok = 0;
         const int * td = dv.up(&tok, 1);
@@ -100,7 +84,7 @@ void quantize_row(const float * x, void * y, int k) {
     try {
         if (k % 32) throw lvk::Error("k must be a multiple of 32");
         if (k == 0) return;
-        DevBufs dv;
+        lvk::Scratch dv;
         const int nb = k / 32;
         const float * xd = dv.up(x, (size_t) k);
         lvk::ActQ a;
@@ -123,7 +107,7 @@ void vec_dot(const int n, float * s, const void * x, const void * y) {
         const int nb = n / 32;
         const int K = (n + 255) / 256 * 256, NB = K / 32, M = 16;
         if (K == 0) { *s = 0.0f; return; }
-        DevBufs dv;
+        lvk::Scratch dv;
         const size_t bb = block_bytes(QT);
         std::vector<uint8_t> rows((size_t) M * NB * bb, 0);
         std::memcpy(rows.data(), x, (size_t) nb * bb);

@@ -602,7 +602,7 @@ int lvk_eval_sample(struct llama_context * ctx, int token, int n_past, const int
     if (ctx->split || c.logits_all || k > lvk::SAMPLE_CAP || n_last > lvk::SAMPLE_MAX_LAST || n_vocab > lvk::SAMPLE_MAX_VOCAB)
         return host_path();
     int64_t t0 = lvk::now_us();
-    lvk::SampleParams & sp = *c.samp_h;
+    lvk::SampleParams & sp = c.samp_h[0];
     sp.k = k;
     sp.n_last = n_last;
     sp.scale = 1.0f / temp;            // llama.cpp:1398
@@ -617,7 +617,7 @@ int lvk_eval_sample(struct llama_context * ctx, int token, int n_past, const int
     c.t_eval_us += lvk::now_us() - t0;
     c.n_eval++;
     t0 = lvk::now_us();
-    int r = lvk::sample_from_candidates(*c.sout_h, k, top_p, c.rng);
+    int r = lvk::sample_from_candidates(c.sout_h[0], k, top_p, c.rng);
     if (r < 0) {
         try {
             c.fetch_logits();

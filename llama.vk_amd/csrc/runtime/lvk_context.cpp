@@ -61,53 +61,15 @@ void host_rope_table(std::vector<float2> & rt, size_t n_ctx, size_t hd) {
 // forces the table.
 int pick_exp_mode(const uint16_t * exp_tab_d) {
     if (getenv("LVK_EXP_TABLE")) return 0;
-    int * bad_d = nullptr;
-    LVK_HIP(hipMalloc((void **) &bad_d, 2 * sizeof(int)));
+    const DevPtr<int> bad_d = dev_alloc<int>(2);
     int bad[2] = {-1, -1};
-    const hipError_t e1 = exp_check(exp_tab_d, bad_d, nullptr);
-    const hipError_t e2 = e1 == hipSuccess ? hipMemcpy(bad, bad_d, sizeof(bad), hipMemcpyDeviceToHost) : e1;
-    (void) hipFree(bad_d);
-    LVK_HIP(e2);
+    LVK_HIP(exp_check(exp_tab_d, bad_d.get(), nullptr));
+    LVK_HIP(hipMemcpy(bad, bad_d.get(), sizeof(bad), hipMemcpyDeviceToHost));
     return bad[1] == 0 ? 2 : bad[0] == 0 ? 1 : 0;
 }
 
-Context::~Context() {
-    if (graph_exec) (void) hipGraphExecDestroy(graph_exec);
-    if (graph) (void) hipGraphDestroy(graph);
-    if (graph_greedy_exec) (void) hipGraphExecDestroy(graph_greedy_exec);
-    if (graph_greedy) (void) hipGraphDestroy(graph_greedy);
-    if (graph_sample_exec) (void) hipGraphExecDestroy(graph_sample_exec);
-    if (graph_sample) (void) hipGraphDestroy(graph_sample);
-    if (graph_chain_exec) (void) hipGraphExecDestroy(graph_chain_exec);
-    if (graph_chain) (void) hipGraphDestroy(graph_chain);
-    drop_rows_graph();
-    for (void * p : {(void *) rc_tok_d, (void *) rc_dig_d, (void *) rc_forced_d, (void *) rc_ctl_d})
-        if (p) (void) hipFree(p);
-    for (void * p : {(void *) rc_tok_h, (void *) rc_dig_h, (void *) rc_forced_h, (void *) rc_ctl_h})
-        if (p) (void) hipHostFree(p);
-    for (void * p : {(void *) sr_rec_d, (void *) sr_pool_d})
-        if (p) (void) hipFree(p);
-    for (void * p : {(void *) sr_out_h, (void *) sr_rec_h, (void *) sr_pool_h})
-        if (p) (void) hipHostFree(p);
-    if (chain_h) (void) hipHostFree(chain_h);
-    if (chain_ctl_h) (void) hipHostFree(chain_ctl_h);
-    if (forced_h) (void) hipHostFree(forced_h);
-    if (digest_h) (void) hipHostFree(digest_h);
-    if (samp_h) (void) hipHostFree(samp_h);
-    if (sout_h) (void) hipHostFree(sout_h);
-    if (greedy_h) (void) hipHostFree(greedy_h);
-    for (SeqKV & s : seq_kv) { (void) hipFree(s.kc); (void) hipFree(s.vc); }
-    if (slots_d) (void) hipFree(slots_d);
-    if (rows_d) (void) hipFree(rows_d);
-    if (amax_d) (void) hipFree(amax_d);
-    if (rows_h) (void) hipHostFree(rows_h);
-    for (auto & e : ev_pool) { (void) hipEventDestroy(e.first); (void) hipEventDestroy(e.second); }
-    if (sp_h) (void) hipHostFree(sp_h);
-    if (tok_h) (void) hipHostFree(tok_h);
-    if (err_h) (void) hipHostFree(err_h);
-    if (stream) (void) hipStreamDestroy(stream);
-}
-
+// Every allocation lands in a member that owns it (or in the model's arena), so a throw part-way
+// frees what came before it when the half-built Context is destroyed.
 void Context::init(const llama_context_params & p) {
     // the caller's window (llama.h accepts any positive n_ctx); buffers and kernels use it
     // rounded up to the 32-position attention tile, at least 128 (positions past the
@@ -170,28 +132,28 @@ void Context::init(const llama_context_params & p) {
     emb_d = (float *) model.alloc(E * 4);
     sp_d = (StepParams *) model.alloc(sizeof(StepParams));
     tok_d = (int *) model.alloc(C * 4);
-    LVK_HIP(hipHostMalloc((void **) &sp_h, (1 + C) * sizeof(StepParams), hipHostMallocDefault));
-    LVK_HIP(hipHostMalloc((void **) &tok_h, C * 4, hipHostMallocDefault));
+    sp_h = pinned_alloc<StepParams>(1 + C);
+    tok_h = pinned_alloc<int>(C);
     LVK_HIP(hipGetDevice(&device));
-    LVK_HIP(hipHostMalloc((void **) &err_h, 64, hipHostMallocMapped | hipHostMallocCoherent));
-    *err_h = 0;
-    LVK_HIP(hipHostGetDevicePointer((void **) &err_d, err_h, 0));
+    err_h = mapped_alloc<unsigned>(16);
+    err_h[0] = 0;
+    err_d = device_address(err_h);
     greedy_d = (int *) model.alloc(4);
     chain_d = (int *) model.alloc((CHAIN_HDR + C) * 4);
     forced_d = (int *) model.alloc(C * 4);
     digest_d = (unsigned long long *) model.alloc(C * 8);
-    LVK_HIP(hipHostMalloc((void **) &chain_h, C * 4, hipHostMallocDefault));
-    LVK_HIP(hipHostMalloc((void **) &chain_ctl_h, CHAIN_HDR * 4, hipHostMallocDefault));
-    LVK_HIP(hipHostMalloc((void **) &forced_h, C * 4, hipHostMallocDefault));
-    LVK_HIP(hipHostMalloc((void **) &digest_h, C * 8, hipHostMallocDefault));
+    chain_h = pinned_alloc<int>(C);
+    chain_ctl_h = pinned_alloc<int>(CHAIN_HDR);
+    forced_h = pinned_alloc<int>(C);
+    digest_h = pinned_alloc<unsigned long long>(C);
     // the device argmax also stores the token straight into host-mapped memory
-    LVK_HIP(hipHostMalloc((void **) &greedy_h, 64, hipHostMallocMapped | hipHostMallocCoherent));
-    LVK_HIP(hipHostGetDevicePointer((void **) &greedy_hd, greedy_h, 0));
+    greedy_h = mapped_alloc<int>(16);
+    greedy_hd = device_address(greedy_h);
     samp_d = (SampleParams *) model.alloc(sizeof(SampleParams));
-    LVK_HIP(hipHostMalloc((void **) &samp_h, sizeof(SampleParams), hipHostMallocDefault));
-    std::memset(samp_h, 0, sizeof(SampleParams));
-    LVK_HIP(hipHostMalloc((void **) &sout_h, sizeof(SampleOut), hipHostMallocMapped | hipHostMallocCoherent));
-    LVK_HIP(hipHostGetDevicePointer((void **) &sout_d, sout_h, 0));
+    samp_h = pinned_alloc<SampleParams>(1);
+    std::memset(samp_h.get(), 0, sizeof(SampleParams));
+    sout_h = mapped_alloc<SampleOut>(1);
+    sout_d = device_address(sout_h);
 
     // fp16 exp / silu tables (ggml.c:2915-2927), built with this host's glibc
     std::vector<uint16_t> te, ts;
@@ -206,15 +168,15 @@ void Context::init(const llama_context_params & p) {
     rope = (float2 *) model.alloc(rt.size() * sizeof(float2));
     LVK_HIP(hipMemcpy(rope, rt.data(), rt.size() * sizeof(float2), hipMemcpyHostToDevice));
 
-    LVK_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    LVK_HIP(hipStreamCreateWithFlags(&stream.s, hipStreamNonBlocking));
     logits.reserve(logits_all ? C * V : V);
     if (want_embedding) embedding.resize(E);
 }
 
 void Context::check_device_error() {
-    const unsigned e = __atomic_load_n(err_h, __ATOMIC_ACQUIRE);
+    const unsigned e = __atomic_load_n(err_h.get(), __ATOMIC_ACQUIRE);
     if (e == LVK_ERR_NONE) return;
-    __atomic_store_n(err_h, 0u, __ATOMIC_RELEASE);
+    __atomic_store_n(err_h.get(), 0u, __ATOMIC_RELEASE);
     logits_valid = false;
     throw Error(e == LVK_ERR_ATTN_SPIN ? "llama.vk_amd: decode attention: a workgroup wait timed out (results discarded)"
                                        : "llama.vk_amd: a kernel wait timed out (results discarded)");
@@ -226,16 +188,14 @@ void Context::timed_launch(int cls, double bytes, const std::function<hipError_t
         return;
     }
     if (ev_used == ev_pool.size()) {
-        hipEvent_t a, b;
-        LVK_HIP(hipEventCreate(&a));
-        LVK_HIP(hipEventCreate(&b));
-        ev_pool.push_back({a, b});
+        Event a = make_event(), b = make_event();
+        ev_pool.emplace_back(std::move(a), std::move(b));
         ev_class.push_back(0);
     }
     auto & e = ev_pool[ev_used];
     ev_class[ev_used] = cls;
     ++ev_used;
-    g_launch_events = {e.first, e.second};
+    g_launch_events = {e.first.get(), e.second.get()};
     const hipError_t err = fn();
     g_launch_events = {};
     LVK_HIP(err);
@@ -246,7 +206,7 @@ void Context::timed_launch(int cls, double bytes, const std::function<hipError_t
 void Context::collect_profile() {
     for (size_t i = 0; i < ev_used; ++i) {
         float ms = 0.0f;
-        LVK_HIP(hipEventElapsedTime(&ms, ev_pool[i].first, ev_pool[i].second));
+        LVK_HIP(hipEventElapsedTime(&ms, ev_pool[i].first.get(), ev_pool[i].second.get()));
         prof.ms[ev_class[i]] += ms;
     }
     ev_used = 0;
@@ -283,10 +243,12 @@ bool Context::use_batched(int n) const {
 // and on a KV slot each, so the fused QKV epilogues, which place row t at sp->n_past + t of slot
 // 0, are not used: QKV is stored to qkv32, launch_rope_kv_rows appends every row's K / V, and one
 // launch_attention_rows serves all rows.
-void Context::enqueue_forward(int n, bool last_only, const int * tok_src, int logit_row, bool head, bool embed, bool rows) {
+void Context::enqueue_forward(const Forward & f) {
     const HParams & hp = model.hp;
-    if (!tok_src) tok_src = tok_d;
-    float * const logits_out = logits_d + (size_t) logit_row * hp.n_vocab;
+    const int n = f.n;
+    const bool last_only = f.last_only, head = f.head, embed = f.embed, rows = f.rows;
+    const int * tok_src = f.tok_src ? f.tok_src : tok_d;
+    float * const logits_out = logits_d + (size_t) f.logit_row * hp.n_vocab;
     const int E = (int) hp.n_embd, H = (int) hp.n_head, hd = E / H, F = (int) hp.n_ff(), V = (int) hp.n_vocab;
     const int qt = model.qtype;
     const bool batched = use_batched(n);
@@ -335,9 +297,9 @@ void Context::enqueue_forward(int n, bool last_only, const int * tok_src, int lo
         const size_t layer_off = il * (size_t) n_ctx * E;
         auto rows_rope_attn = [&] {
             timed_launch(K_QKV, 0, [&] {
-                return launch_rope_kv_rows(qkv32, n, E, hd, rope, rows_d, slots_d, layer_off, n_ctx, q16, stream);
+                return launch_rope_kv_rows(qkv32, n, E, hd, rope, rows_d.get(), slots_d.get(), layer_off, n_ctx, q16, stream);
             });
-            timed_launch(K_ATTN, 0, [&] { return launch_attention_rows(at, rows_d, slots_d, layer_off, stream); });
+            timed_launch(K_ATTN, 0, [&] { return launch_attention_rows(at, rows_d.get(), slots_d.get(), layer_off, stream); });
         };
         if (batched) {
             ActImage in = act(K_QKV, x, ly.attn_norm, E);
@@ -426,41 +388,35 @@ void Context::enqueue_forward(int n, bool last_only, const int * tok_src, int lo
         LVK_HIP(launch_rmsnorm_rows(x + (size_t) (n - 1) * E, model.norm, E, 1, emb_d, stream));
 }
 
-void Context::build_graph(int kind) {
+void Context::build_graph(DecodeGraph kind) {
     // one replay per token: the step block H2D, the forward pass and the logits D2H
     // (both host buffers page-locked, the logits one sized before the capture); the
     // greedy variant ends in the device argmax (token into host-mapped memory), the sample
     // variant copies the sampler block in and ends in the device top-k candidates
-    LVK_HIP(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-    try {
-        if (kind == 3) {
+    const int V = (int) model.hp.n_vocab;
+    capture(stream, graph_of(kind), [&] {
+        if (kind == DecodeGraph::CHAIN) {
             // a chained step: the step block and x were left by the previous step (or the
             // call's setup); the argmax advances both for the next replay
-            enqueue_forward(1, true, nullptr, 0, true, false);
-            LVK_HIP(launch_argmax_step(logits_d, (int) model.hp.n_vocab, sp_d, chain_d, forced_d, digest_d, model.tok_emb, model.emb_type,
+            Forward f;
+            f.embed = false;
+            enqueue_forward(f);
+            LVK_HIP(launch_argmax_step(logits_d, V, sp_d, chain_d, forced_d, digest_d, model.tok_emb, model.emb_type,
                                        (int) model.hp.n_embd, x, stream));
-        } else {
-            LVK_HIP(hipMemcpyAsync(sp_d, sp_h, sizeof(StepParams), hipMemcpyHostToDevice, stream));
-            if (kind == 2) LVK_HIP(hipMemcpyAsync(samp_d, samp_h, sizeof(SampleParams), hipMemcpyHostToDevice, stream));
-            enqueue_forward(1, true);
-            if (kind == 1) {
-                enqueue_argmax();
-            } else if (kind == 2) {
-                LVK_HIP(launch_sample_cand(logits_d, (int) model.hp.n_vocab, samp_d, sout_d, stream));
-            } else if (model.has_head) {
-                LVK_HIP(hipMemcpyAsync(logits.data(), logits_d, sizeof(float) * logits.size(), hipMemcpyDeviceToHost,
-                                       stream));
-            }
+            return;
         }
-    } catch (...) {
-        hipGraph_t g;
-        (void) hipStreamEndCapture(stream, &g);
-        throw;
-    }
-    hipGraph_t & g = kind == 1 ? graph_greedy : kind == 2 ? graph_sample : kind == 3 ? graph_chain : graph;
-    hipGraphExec_t & ge = kind == 1 ? graph_greedy_exec : kind == 2 ? graph_sample_exec : kind == 3 ? graph_chain_exec : graph_exec;
-    LVK_HIP(hipStreamEndCapture(stream, &g));
-    LVK_HIP(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
+        LVK_HIP(hipMemcpyAsync(sp_d, sp_h.get(), sizeof(StepParams), hipMemcpyHostToDevice, stream));
+        if (kind == DecodeGraph::SAMPLE)
+            LVK_HIP(hipMemcpyAsync(samp_d, samp_h.get(), sizeof(SampleParams), hipMemcpyHostToDevice, stream));
+        enqueue_forward(Forward{});
+        if (kind == DecodeGraph::GREEDY) {
+            enqueue_argmax();
+        } else if (kind == DecodeGraph::SAMPLE) {
+            LVK_HIP(launch_sample_cand(logits_d, V, samp_d, sout_d, stream));
+        } else if (model.has_head) {
+            LVK_HIP(hipMemcpyAsync(logits.data(), logits_d, sizeof(float) * logits.size(), hipMemcpyDeviceToHost, stream));
+        }
+    });
 }
 
 // greedy token of the last logits row: the device word feeds the stage link (lvk_split.cpp),
@@ -480,7 +436,7 @@ int Context::eval_greedy(int token, int n_past) {
     begin_eval_safe(&token, 1, n_past, part);
     end_eval(true);
     kv_n = n_past + 1;
-    return *greedy_h;
+    return greedy_h[0];
 }
 
 // the step counter of the next device step (StepParams::seq); before it would run past the
@@ -514,8 +470,8 @@ int Context::decode_chain(const int * tokens, int n_tokens, int n_past, int n_st
         if (tokens[i] < 0 || tokens[i] >= (int) model.hp.n_vocab) throw Error("llama.vk_amd: token id out of range");
     if (!use_graph || profiling)
         throw Error("llama.vk_amd: chained decode needs the launch-per-phase decode graph");
-    try {
-        StepParams * sh = sp_h;
+    drain_on_error(false, true, [&] {
+        StepParams * sh = sp_h.get();
         sh->n_past = n_past;
         sh->n_tokens = 1;
         sh->pad0 = tokens[0];
@@ -525,26 +481,22 @@ int Context::decode_chain(const int * tokens, int n_tokens, int n_past, int n_st
         chain_ctl_h[1] = n_tokens > 1 ? n_tokens : 0;
         chain_ctl_h[2] = digests ? 1 : 0;
         chain_ctl_h[3] = 0;
-        LVK_HIP(hipMemcpyAsync(chain_d, chain_ctl_h, CHAIN_HDR * 4, hipMemcpyHostToDevice, stream));
+        LVK_HIP(hipMemcpyAsync(chain_d, chain_ctl_h.get(), CHAIN_HDR * 4, hipMemcpyHostToDevice, stream));
         if (n_tokens > 1) {
-            std::memcpy(forced_h, tokens, sizeof(int) * (size_t) n_tokens);
-            LVK_HIP(hipMemcpyAsync(forced_d, forced_h, sizeof(int) * (size_t) n_tokens, hipMemcpyHostToDevice, stream));
+            std::memcpy(forced_h.get(), tokens, sizeof(int) * (size_t) n_tokens);
+            LVK_HIP(hipMemcpyAsync(forced_d, forced_h.get(), sizeof(int) * (size_t) n_tokens, hipMemcpyHostToDevice, stream));
         }
         LVK_HIP(launch_embed(model.tok_emb, model.emb_type, (int) model.hp.n_embd, &sp_d->pad0, 1, x, stream));
-        if (!graph_chain_exec) build_graph(3);
-        for (int i = 0; i < n_steps; ++i) LVK_HIP(hipGraphLaunch(graph_chain_exec, stream));
-        LVK_HIP(hipMemcpyAsync(chain_h, chain_d + CHAIN_HDR, sizeof(int) * (size_t) n_steps, hipMemcpyDeviceToHost, stream));
+        if (!graph_of(DecodeGraph::CHAIN)) build_graph(DecodeGraph::CHAIN);
+        for (int i = 0; i < n_steps; ++i) LVK_HIP(graph_of(DecodeGraph::CHAIN).launch(stream));
+        LVK_HIP(hipMemcpyAsync(chain_h.get(), chain_d + CHAIN_HDR, sizeof(int) * (size_t) n_steps, hipMemcpyDeviceToHost, stream));
         if (digests)
-            LVK_HIP(hipMemcpyAsync(digest_h, digest_d, 8 * (size_t) n_steps, hipMemcpyDeviceToHost, stream));
-    } catch (...) {
-        (void) hipStreamSynchronize(stream);
-        logits_valid = false;
-        throw;
-    }
+            LVK_HIP(hipMemcpyAsync(digest_h.get(), digest_d, 8 * (size_t) n_steps, hipMemcpyDeviceToHost, stream));
+    });
     end_eval(true);
     kv_n = n_past + n_steps;
-    std::memcpy(out, chain_h, sizeof(int) * (size_t) n_steps);
-    if (digests) std::memcpy(digests, digest_h, 8 * (size_t) n_steps);
+    std::memcpy(out, chain_h.get(), sizeof(int) * (size_t) n_steps);
+    if (digests) std::memcpy(digests, digest_h.get(), 8 * (size_t) n_steps);
     return out[n_steps - 1];
 }
 
@@ -579,14 +531,7 @@ void Context::eval(const int * tokens, int n, int n_past) {
 // work already queued drains, the step blocks are released and the host logits are marked
 // stale before the error propagates (llama_get_logits then refuses them)
 void Context::begin_eval_safe(const int * tokens, int n, int n_past, const EvalPart & part) {
-    try {
-        begin_eval(tokens, n, n_past, part);
-    } catch (...) {
-        (void) hipStreamSynchronize(stream);
-        sp_next = 1;
-        logits_valid = false;
-        throw;
-    }
+    drain_on_error(true, true, [&] { begin_eval(tokens, n, n_past, part); });
 }
 
 void Context::begin_eval(const int * tokens, int n, int n_past, const EvalPart & part) {
@@ -601,7 +546,7 @@ void Context::begin_eval(const int * tokens, int n, int n_past, const EvalPart &
         if (!tokens) throw Error("llama.vk_amd: the first stage needs tokens");
         for (int i = 0; i < n; ++i)
             if (tokens[i] < 0 || tokens[i] >= V) throw Error("llama.vk_amd: token id out of range");
-        std::memcpy(tok_h + part.tok_off, tokens, sizeof(int) * (size_t) n);
+        std::memcpy(tok_h.get() + part.tok_off, tokens, sizeof(int) * (size_t) n);
     }
     const bool last_only = !logits_all;
     const bool single = part.n_total < 0 || part.n_total == n;
@@ -609,7 +554,7 @@ void Context::begin_eval(const int * tokens, int n, int n_past, const EvalPart &
     // the graphs read step block 0; eager slices each take their own (the H2D copy reads
     // the pinned block when it executes, after the host may have queued further slices)
     if (!graph_ok && sp_next > n_ctx) throw Error("llama.vk_amd: too many slices before a sync");
-    StepParams * sh = graph_ok ? sp_h : sp_h + sp_next++;
+    StepParams * sh = &sp_h[graph_ok ? 0 : sp_next++];
     sh->n_past = n_past;
     sh->n_tokens = n;
     sh->pad0 = (n == 1 && model.has_embed) ? tokens[0] : 0;
@@ -617,17 +562,22 @@ void Context::begin_eval(const int * tokens, int n, int n_past, const EvalPart &
     if (model.has_head && part.tok_off == 0)   // within the reserve: the pointer never moves
         logits.resize((size_t) (last_only ? 1 : n_total) * V);
     if (graph_ok) {
-        const int kind = part.greedy ? 1 : part.sample ? 2 : 0;
-        hipGraphExec_t & ge = kind == 1 ? graph_greedy_exec : kind == 2 ? graph_sample_exec : graph_exec;
-        if (!ge) build_graph(kind);
-        LVK_HIP(hipGraphLaunch(ge, stream));
+        const DecodeGraph kind = part.greedy ? DecodeGraph::GREEDY : part.sample ? DecodeGraph::SAMPLE : DecodeGraph::LOGITS;
+        if (!graph_of(kind)) build_graph(kind);
+        LVK_HIP(graph_of(kind).launch(stream));
     } else {
         LVK_HIP(hipMemcpyAsync(sp_d, sh, sizeof(StepParams), hipMemcpyHostToDevice, stream));
-        if (part.sample) LVK_HIP(hipMemcpyAsync(samp_d, samp_h, sizeof(SampleParams), hipMemcpyHostToDevice, stream));
+        if (part.sample) LVK_HIP(hipMemcpyAsync(samp_d, samp_h.get(), sizeof(SampleParams), hipMemcpyHostToDevice, stream));
         if (n > 1)
-            LVK_HIP(hipMemcpyAsync(tok_d + part.tok_off, tok_h + part.tok_off, sizeof(int) * (size_t) n,
+            LVK_HIP(hipMemcpyAsync(tok_d + part.tok_off, tok_h.get() + part.tok_off, sizeof(int) * (size_t) n,
                                    hipMemcpyHostToDevice, stream));
-        enqueue_forward(n, last_only, tok_d + part.tok_off, last_only ? 0 : part.tok_off, part.head);
+        Forward f;
+        f.n = n;
+        f.last_only = last_only;
+        f.tok_src = tok_d + part.tok_off;
+        f.logit_row = last_only ? 0 : part.tok_off;
+        f.head = part.head;
+        enqueue_forward(f);
         if (part.greedy) {
             enqueue_argmax();
         } else if (part.sample) {
@@ -675,7 +625,7 @@ void Context::kv_set(const uint8_t * src, size_t n) {
 // [L][n_ctx][E] are one pitched block per layer, V [L][E][n_ctx] one short row per
 // (layer, dim).  Only the n_tokens positions move, not the whole cache.
 void Context::kv_copy_from(const Context & src, int n_tokens) {
-    const size_t E = model.hp.n_embd, L = model.layers.size(), C = (size_t) n_ctx;
+    const size_t L = model.layers.size();
     if (src.model.hp.n_embd != model.hp.n_embd || src.model.layers.size() != L || src.n_ctx != n_ctx || src.n_ctx_user != n_ctx_user ||
         src.model.hp.n_head != model.hp.n_head || src.model.layer_begin != model.layer_begin)
         throw Error("lvk_kv_copy: contexts differ in n_embd, n_head, n_layer, layer range or n_ctx");
@@ -687,490 +637,19 @@ void Context::kv_copy_from(const Context & src, int n_tokens) {
     if (src.kv32 != kv32) throw Error("lvk_kv_copy: contexts differ in the KV cache type (f16_kv)");
     if (n_tokens < 0 || n_tokens > n_ctx_user) throw Error("lvk_kv_copy: n_tokens out of range");
     if (n_tokens > 0) {
-        const size_t n = (size_t) n_tokens;
         LVK_HIP(hipStreamSynchronize(src.stream));
-        const size_t es = kv_elem_bytes();
-        LVK_HIP(hipMemcpy2DAsync(kc, C * E * es, src.kc, C * E * es, n * E * es, L, hipMemcpyDeviceToDevice, stream));
-        LVK_HIP(hipMemcpy2DAsync(vc, C * es, src.vc, C * es, n * es, L * E, hipMemcpyDeviceToDevice, stream));
-        LVK_HIP(hipStreamSynchronize(stream));
+        copy_kv_prefix(kc, vc, src.kc, src.vc, n_tokens);
     }
     kv_n = n_tokens;
 }
 
-// KV slots 1..n_seq-1 and, on the first call, the row and slot tables of decode_rows.  Everything
-// new is allocated before anything is committed, so a failure leaves the context as it was.
-void Context::seq_init(int n_seq) {
-    const HParams & hp = model.hp;
-    if (n_seq < 1) throw Error("lvk_seq_init: n_seq must be at least 1");
-    if (kv32) throw Error("lvk_seq_init: batched decode needs the f16 KV cache (f16_kv = true)");
-    if (!model.has_embed || !model.has_head || link) throw Error("lvk_seq_init: not available on a stage context");
-    if (!attention_rows_supported((int) hp.n_embd, (int) hp.n_head, n_ctx))
-        throw Error("lvk_seq_init: batched decode needs head_dim 128");
-    const int have = seq_count();
-    if (n_seq <= have && slots_d) return;
-    const int want = std::max(n_seq, have);
-    const size_t bytes = kv_bytes() / 2, C = (size_t) n_ctx;
-    struct Fresh {      // freed unless committed
-        std::vector<void *> dev;
-        void * host = nullptr;
-        ~Fresh() {
-            for (void * p : dev) (void) hipFree(p);
-            if (host) (void) hipHostFree(host);
-        }
-        void * get(size_t n) {
-            void * p = nullptr;
-            if (hipMalloc(&p, n) != hipSuccess) {
-                (void) hipGetLastError();
-                throw Error("lvk_seq_init: out of device memory");
-            }
-            dev.push_back(p);
-            return p;
-        }
-    } fresh;
-    std::vector<SeqKV> add((size_t) (want - have));
-    for (SeqKV & s : add) {
-        s.kc = (uint16_t *) fresh.get(bytes);
-        s.vc = (uint16_t *) fresh.get(bytes);
-        LVK_HIP(hipMemset(s.kc, 0, bytes));
-        LVK_HIP(hipMemset(s.vc, 0, bytes));
-    }
-    // the new slots' generators start from the context's seed; the existing ones stay as they are
-    std::vector<std::mt19937> gens;
-    gens.reserve((size_t) want - 1);
-    gens.assign(seq_rng.begin(), seq_rng.end());
-    gens.resize((size_t) want - 1, std::mt19937((unsigned) seed));
-    std::vector<SeqSlot> table;
-    table.push_back({kc, vc});
-    for (const SeqKV & s : seq_kv) table.push_back({s.kc, s.vc});
-    for (const SeqKV & s : add) table.push_back({s.kc, s.vc});
-    SeqSlot * table_d = (SeqSlot *) fresh.get(table.size() * sizeof(SeqSlot));
-    SeqRow * rd = rows_d;
-    int * ad = amax_d;
-    if (!rows_d) {
-        rd = (SeqRow *) fresh.get(C * sizeof(SeqRow));
-        ad = (int *) fresh.get(C * sizeof(int));
-        LVK_HIP(hipHostMalloc(&fresh.host, C * sizeof(SeqRow), hipHostMallocDefault));
-    }
-    LVK_HIP(hipStreamSynchronize(stream));      // nothing in flight reads the old table
-    LVK_HIP(hipMemcpy(table_d, table.data(), table.size() * sizeof(SeqSlot), hipMemcpyHostToDevice));
-    // commit
-    drop_rows_graph();      // its launches hold the old slot table
-    if (slots_d) (void) hipFree(slots_d);
-    slots_d = table_d;
-    if (!rows_d) {
-        rows_d = rd;
-        amax_d = ad;
-        rows_h = (SeqRow *) fresh.host;
-        fresh.host = nullptr;
-    }
-    seq_kv.insert(seq_kv.end(), add.begin(), add.end());
-    seq_rng.swap(gens);
-    fresh.dev.clear();
+void Context::copy_kv_prefix(uint16_t * dk, uint16_t * dv, const uint16_t * sk, const uint16_t * sv, int n_tokens) {
+    const size_t E = model.hp.n_embd, L = model.layers.size(), C = (size_t) n_ctx, n = (size_t) n_tokens, es = kv_elem_bytes();
+    LVK_HIP(hipMemcpy2DAsync(dk, C * E * es, sk, C * E * es, n * E * es, L, hipMemcpyDeviceToDevice, stream));
+    LVK_HIP(hipMemcpy2DAsync(dv, C * es, sv, C * es, n * es, L * E, hipMemcpyDeviceToDevice, stream));
+    LVK_HIP(hipStreamSynchronize(stream));
 }
 
-// positions [0, n_tokens) of every layer's K and V from slot src to slot dst, device to device
-// (the copies of kv_copy_from)
-void Context::seq_copy(int dst, int src, int n_tokens) {
-    if (dst < 0 || dst >= seq_count() || src < 0 || src >= seq_count()) throw Error("lvk_seq_copy: sequence id out of range");
-    if (n_tokens < 0 || n_tokens > seq_n(src)) throw Error("lvk_seq_copy: n_tokens exceeds the source sequence");
-    if (dst != src && n_tokens > 0) {
-        const size_t E = model.hp.n_embd, L = model.layers.size(), C = (size_t) n_ctx, n = (size_t) n_tokens, es = kv_elem_bytes();
-        uint16_t * dk = dst == 0 ? kc : seq_kv[(size_t) dst - 1].kc, * dv = dst == 0 ? vc : seq_kv[(size_t) dst - 1].vc;
-        const uint16_t * sk = src == 0 ? kc : seq_kv[(size_t) src - 1].kc, * sv = src == 0 ? vc : seq_kv[(size_t) src - 1].vc;
-        LVK_HIP(hipMemcpy2DAsync(dk, C * E * es, sk, C * E * es, n * E * es, L, hipMemcpyDeviceToDevice, stream));
-        LVK_HIP(hipMemcpy2DAsync(dv, C * es, sv, C * es, n * es, L * E, hipMemcpyDeviceToDevice, stream));
-        LVK_HIP(hipStreamSynchronize(stream));
-    }
-    seq_n(dst) = n_tokens;
-}
-
-// the argument checks of a batched decode step (decode_rows, decode_rows_sample), messages under
-// the caller's name
-std::vector<int> Context::rows_check(const char * fn, const int * tokens, const int * seqs, const int * pos, int n) {
-    const int V = (int) model.hp.n_vocab;
-    const std::string f = std::string(fn) + ": ";
-    if (!tokens || !seqs || !pos) throw Error(f + "null argument");
-    if (n < 1 || n > n_ctx_user) throw Error(f + "the row count must be in 1..n_ctx");
-    // next[s]: the position the next row of slot s must have (-1: no row yet)
-    std::vector<int> next((size_t) seq_count(), -1);
-    for (int i = 0; i < n; ++i) {
-        if (tokens[i] < 0 || tokens[i] >= V) throw Error(f + "token id out of range");
-        if (seqs[i] < 0 || seqs[i] >= seq_count()) throw Error(f + "sequence id out of range");
-        if (pos[i] < 0 || pos[i] >= n_ctx_user) throw Error(f + "position outside n_ctx");
-        int & nx = next[(size_t) seqs[i]];
-        if (nx < 0 && pos[i] > seq_n(seqs[i])) throw Error(f + "position past the end of its sequence (a hole)");
-        if (nx >= 0 && pos[i] != nx) throw Error(f + "rows of one sequence must have consecutive ascending positions");
-        nx = pos[i] + 1;
-    }
-    return next;
-}
-
-// One batched decode step (lvk_decode_batch).  Every argument is checked before anything is
-// enqueued; the slots' counts move only after the step has completed.
-void Context::decode_rows(const int * tokens, const int * seqs, const int * pos, int n, float * logits_out, int * argmax_out) {
-    const HParams & hp = model.hp;
-    const int V = (int) hp.n_vocab;
-    if (!slots_d) seq_init(1);
-    const std::vector<int> next = rows_check("lvk_decode_batch", tokens, seqs, pos, n);
-    try {
-        if (sp_next > n_ctx) throw Error("llama.vk_amd: too many slices before a sync");
-        StepParams * sh = sp_h + sp_next++;
-        sh->n_past = 0;             // no kernel of this path takes a position from the step block
-        sh->n_tokens = n;
-        sh->pad0 = n == 1 ? tokens[0] : 0;
-        sh->seq = next_seq();
-        std::memcpy(tok_h, tokens, sizeof(int) * (size_t) n);
-        for (int i = 0; i < n; ++i) rows_h[i] = {seqs[i], pos[i]};
-        LVK_HIP(hipMemcpyAsync(sp_d, sh, sizeof(StepParams), hipMemcpyHostToDevice, stream));
-        LVK_HIP(hipMemcpyAsync(tok_d, tok_h, sizeof(int) * (size_t) n, hipMemcpyHostToDevice, stream));
-        LVK_HIP(hipMemcpyAsync(rows_d, rows_h, sizeof(SeqRow) * (size_t) n, hipMemcpyHostToDevice, stream));
-        enqueue_forward(n, false, tok_d, 0, true, true, true);
-        if (argmax_out) {
-            LVK_HIP(launch_argmax_rows(logits_d, V, n, amax_d, stream));
-            LVK_HIP(hipMemcpyAsync(argmax_out, amax_d, sizeof(int) * (size_t) n, hipMemcpyDeviceToHost, stream));
-        }
-        if (logits_out)
-            LVK_HIP(hipMemcpyAsync(logits_out, logits_d, sizeof(float) * (size_t) n * V, hipMemcpyDeviceToHost, stream));
-    } catch (...) {
-        (void) hipStreamSynchronize(stream);
-        sp_next = 1;
-        throw;
-    }
-    // the host logits of llama_get_logits are an earlier eval's: they stay as they are
-    const bool valid = logits_valid;
-    end_eval(true);
-    logits_valid = valid;
-    for (int s = 0; s < seq_count(); ++s)
-        if (next[(size_t) s] >= 0) seq_n(s) = next[(size_t) s];
-}
-
-// room for `rows` sampled rows of a step and `pool` last-n ids: the host-mapped candidates, the
-// records and the pool, on the device and page-locked on the host.  Everything new is allocated
-// before anything is committed (as rows_chain_reserve); a buffer that is large enough stays.
-void Context::rows_sample_reserve(size_t rows, size_t pool) {
-    const bool grow_rows = rows > sr_cap, grow_pool = pool > sr_pool_cap || !sr_pool_d;
-    if (!grow_rows && !grow_pool) return;
-    struct Fresh {      // freed unless committed
-        std::vector<void *> dev, host;
-        ~Fresh() {
-            for (void * p : dev) (void) hipFree(p);
-            for (void * p : host) (void) hipHostFree(p);
-        }
-        void * get(size_t n, int kind) {      // 0 device, 1 pinned, 2 host-mapped
-            void * p = nullptr;
-            const hipError_t e = kind == 0 ? hipMalloc(&p, n)
-                                           : hipHostMalloc(&p, n, kind == 1 ? hipHostMallocDefault
-                                                                            : hipHostMallocMapped | hipHostMallocCoherent);
-            if (e != hipSuccess) {
-                (void) hipGetLastError();
-                throw Error("lvk_decode_batch_sample: out of memory for the sampler's rows");
-            }
-            (kind == 0 ? dev : host).push_back(p);
-            return p;
-        }
-    } fresh;
-    const size_t rcap = grow_rows ? std::max(rows, (size_t) 16) : sr_cap;
-    const size_t pcap = grow_pool ? std::max(std::max(pool, sr_pool_cap), (size_t) 1024) : sr_pool_cap;
-    SampleOut * out_hn = sr_out_h, * out_dn = sr_out_d;
-    SampleRow * rec_hn = sr_rec_h, * rec_dn = sr_rec_d;
-    int * pool_hn = sr_pool_h, * pool_dn = sr_pool_d;
-    if (grow_rows) {
-        out_hn = (SampleOut *) fresh.get(rcap * sizeof(SampleOut), 2);
-        LVK_HIP(hipHostGetDevicePointer((void **) &out_dn, out_hn, 0));
-        rec_hn = (SampleRow *) fresh.get(rcap * sizeof(SampleRow), 1);
-        rec_dn = (SampleRow *) fresh.get(rcap * sizeof(SampleRow), 0);
-    }
-    if (grow_pool) {
-        pool_hn = (int *) fresh.get(pcap * sizeof(int), 1);
-        pool_dn = (int *) fresh.get(pcap * sizeof(int), 0);
-    }
-    LVK_HIP(hipStreamSynchronize(stream));      // nothing in flight uses the old buffers
-    // commit
-    if (grow_rows) {
-        if (sr_rec_d) (void) hipFree(sr_rec_d);
-        for (void * p : {(void *) sr_out_h, (void *) sr_rec_h})
-            if (p) (void) hipHostFree(p);
-        sr_out_h = out_hn; sr_out_d = out_dn;
-        sr_rec_h = rec_hn; sr_rec_d = rec_dn;
-        sr_cap = rcap;
-    }
-    if (grow_pool) {
-        if (sr_pool_d) (void) hipFree(sr_pool_d);
-        if (sr_pool_h) (void) hipHostFree(sr_pool_h);
-        sr_pool_h = pool_hn; sr_pool_d = pool_dn;
-        sr_pool_cap = pcap;
-    }
-    fresh.dev.clear();
-    fresh.host.clear();
-}
-
-// One batched decode step that ends in the sampler (lvk_decode_batch_sample): decode_rows' forward
-// pass, enqueued eagerly; launch_argmax_rows over the span of rows that ask for a greedy token
-// (temp <= 0); one launch_sample_cand_rows for the rows that sample within the device limits; one
-// stream sync; then, in row order, the host tail of lvk_eval_sample over each row's candidates
-// with the generator of the row's slot.  A row with ties, NaN, overflow, top_k <= 0 or >
-// SAMPLE_CAP, or a window > SAMPLE_MAX_LAST has its own logits row copied to the host and takes
-// sample_logits there with the same generator (n_sample_fallback counts it); no other row notices.
-// Every argument is checked before anything is enqueued; the slots' counts move after the step
-// has completed.  The rows count into the eval timings, the sampled rows into the sample timings.
-void Context::decode_rows_sample(const int * tokens, const int * seqs, const int * pos, int n, const lvk_row_sample * rows,
-                                 int * out_tokens) {
-    const int64_t t0 = now_us();
-    const int V = (int) model.hp.n_vocab;
-    if (!slots_d) seq_init(1);
-    const std::vector<int> next = rows_check("lvk_decode_batch_sample", tokens, seqs, pos, n);
-    if (!rows || !out_tokens) throw Error("lvk_decode_batch_sample: null argument");
-    enum : char { NONE, GREEDY, DEVICE, HOST };
-    std::vector<char> kind((size_t) n, NONE);
-    std::vector<int> top((size_t) n, 0);      // the reference's k: top_k, or all of them
-    size_t n_dev = 0, n_pool = 0;
-    int n_samp = 0, g_lo = n, g_hi = -1;
-    for (int i = 0; i < n; ++i) {
-        const lvk_row_sample & r = rows[i];
-        if (!r.sample) continue;
-        if (r.n_last < 0 || (r.n_last > 0 && !r.last_n)) throw Error("lvk_decode_batch_sample: bad last-n window");
-        ++n_samp;
-        const int k = top[(size_t) i] = r.top_k > 0 ? std::min(r.top_k, V) : V;
-        if (r.temp <= 0) {                              // llama.cpp:1382-1394
-            kind[(size_t) i] = GREEDY;
-            g_lo = std::min(g_lo, i);
-            g_hi = i;
-        } else if (k > SAMPLE_CAP || r.n_last > SAMPLE_MAX_LAST || V > SAMPLE_MAX_VOCAB) {
-            kind[(size_t) i] = HOST;
-        } else {
-            kind[(size_t) i] = DEVICE;
-            ++n_dev;
-            n_pool += (size_t) r.n_last;
-        }
-    }
-    if (n_dev) rows_sample_reserve(n_dev, n_pool);
-    std::vector<int> amax((size_t) n, -1), slot_of((size_t) n, -1);
-    try {
-        if (sp_next > n_ctx) throw Error("llama.vk_amd: too many slices before a sync");
-        StepParams * sh = sp_h + sp_next++;
-        sh->n_past = 0;             // no kernel of this path takes a position from the step block
-        sh->n_tokens = n;
-        sh->pad0 = n == 1 ? tokens[0] : 0;
-        sh->seq = next_seq();
-        std::memcpy(tok_h, tokens, sizeof(int) * (size_t) n);
-        for (int i = 0; i < n; ++i) rows_h[i] = {seqs[i], pos[i]};
-        size_t j = 0, off = 0;
-        for (int i = 0; i < n; ++i) {
-            if (kind[(size_t) i] != DEVICE) continue;
-            const lvk_row_sample & r = rows[i];
-            sr_rec_h[j] = {i, top[(size_t) i], r.n_last, (int) off, 1.0f / r.temp /* llama.cpp:1398 */, r.repeat_penalty};
-            if (r.n_last > 0) std::memcpy(sr_pool_h + off, r.last_n, sizeof(int) * (size_t) r.n_last);
-            off += (size_t) r.n_last;
-            slot_of[(size_t) i] = (int) j++;
-        }
-        LVK_HIP(hipMemcpyAsync(sp_d, sh, sizeof(StepParams), hipMemcpyHostToDevice, stream));
-        LVK_HIP(hipMemcpyAsync(tok_d, tok_h, sizeof(int) * (size_t) n, hipMemcpyHostToDevice, stream));
-        LVK_HIP(hipMemcpyAsync(rows_d, rows_h, sizeof(SeqRow) * (size_t) n, hipMemcpyHostToDevice, stream));
-        if (n_dev) {
-            LVK_HIP(hipMemcpyAsync(sr_rec_d, sr_rec_h, sizeof(SampleRow) * n_dev, hipMemcpyHostToDevice, stream));
-            if (n_pool) LVK_HIP(hipMemcpyAsync(sr_pool_d, sr_pool_h, sizeof(int) * n_pool, hipMemcpyHostToDevice, stream));
-        }
-        enqueue_forward(n, false, tok_d, 0, true, true, true);
-        if (g_hi >= 0) {
-            const size_t m = (size_t) (g_hi - g_lo + 1);
-            LVK_HIP(launch_argmax_rows(logits_d + (size_t) g_lo * V, V, (int) m, amax_d + g_lo, stream));
-            LVK_HIP(hipMemcpyAsync(amax.data() + g_lo, amax_d + g_lo, sizeof(int) * m, hipMemcpyDeviceToHost, stream));
-        }
-        if (n_dev) LVK_HIP(launch_sample_cand_rows(logits_d, V, sr_rec_d, sr_pool_d, (int) n_dev, sr_out_d, stream));
-    } catch (...) {
-        (void) hipStreamSynchronize(stream);
-        sp_next = 1;
-        throw;
-    }
-    // the host logits of llama_get_logits are an earlier eval's: they stay as they are
-    const bool valid = logits_valid;
-    end_eval(true);
-    logits_valid = valid;
-    for (int s = 0; s < seq_count(); ++s)
-        if (next[(size_t) s] >= 0) seq_n(s) = next[(size_t) s];
-    const int64_t t1 = now_us();
-    t_eval_us += t1 - t0;       // n decode evals (llama.cpp:1186-1195)
-    n_eval += n;
-    std::vector<float> row;
-    for (int i = 0; i < n; ++i) {
-        const lvk_row_sample & r = rows[i];
-        int tok = -1;
-        if (kind[(size_t) i] == GREEDY) tok = amax[(size_t) i];
-        else if (kind[(size_t) i] == DEVICE)
-            tok = sample_from_candidates(sr_out_h[slot_of[(size_t) i]], top[(size_t) i], r.top_p, seq_gen(seqs[i]));
-        if (tok < 0 && (kind[(size_t) i] == DEVICE || kind[(size_t) i] == HOST)) {
-            row.resize((size_t) V);
-            LVK_HIP(hipMemcpy(row.data(), logits_d + (size_t) i * V, sizeof(float) * (size_t) V, hipMemcpyDeviceToHost));
-            tok = sample_logits(row.data(), V, r.last_n, r.n_last, r.top_k, r.top_p, r.temp, r.repeat_penalty, seq_gen(seqs[i]));
-            n_sample_fallback++;
-        }
-        out_tokens[i] = tok;
-    }
-    t_sample_us += now_us() - t1;
-    n_sample += n_samp;
-}
-
-void Context::drop_rows_graph() {
-    if (graph_rows_exec) (void) hipGraphExecDestroy(graph_rows_exec);
-    if (graph_rows) (void) hipGraphDestroy(graph_rows);
-    graph_rows_exec = nullptr;
-    graph_rows = nullptr;
-    graph_rows_n = 0;
-}
-
-// room for `entries` = n_steps * n tokens, digests and forced tokens of a chained batched decode,
-// on the device and page-locked on the host, and on the first call the control block.  Everything
-// new is allocated before anything is committed (as seq_init); the step graph holds the old
-// addresses, so it goes with them.
-void Context::rows_chain_reserve(size_t entries) {
-    if (entries <= rc_cap && rc_ctl_d) return;
-    const size_t cap = std::max(std::max(entries, rc_cap), (size_t) n_ctx);
-    struct Fresh {      // freed unless committed
-        std::vector<void *> dev, host;
-        ~Fresh() {
-            for (void * p : dev) (void) hipFree(p);
-            for (void * p : host) (void) hipHostFree(p);
-        }
-        void * get(size_t n, bool pinned) {
-            void * p = nullptr;
-            const hipError_t e = pinned ? hipHostMalloc(&p, n, hipHostMallocDefault) : hipMalloc(&p, n);
-            if (e != hipSuccess) {
-                (void) hipGetLastError();
-                throw Error("lvk_decode_batch_chain: out of memory for the step outputs");
-            }
-            (pinned ? host : dev).push_back(p);
-            return p;
-        }
-    } fresh;
-    int * tok_dn = (int *) fresh.get(cap * sizeof(int), false), * tok_hn = (int *) fresh.get(cap * sizeof(int), true);
-    auto * dig_dn = (unsigned long long *) fresh.get(cap * 8, false), * dig_hn = (unsigned long long *) fresh.get(cap * 8, true);
-    int * for_dn = (int *) fresh.get(cap * sizeof(int), false), * for_hn = (int *) fresh.get(cap * sizeof(int), true);
-    int * ctl_dn = rc_ctl_d, * ctl_hn = rc_ctl_h;
-    if (!rc_ctl_d) {
-        ctl_dn = (int *) fresh.get((2 + (size_t) n_ctx) * sizeof(int), false);
-        ctl_hn = (int *) fresh.get((2 + (size_t) n_ctx) * sizeof(int), true);
-    }
-    LVK_HIP(hipStreamSynchronize(stream));      // nothing in flight uses the old buffers
-    // commit
-    drop_rows_graph();
-    for (void * p : {(void *) rc_tok_d, (void *) rc_dig_d, (void *) rc_forced_d})
-        if (p) (void) hipFree(p);
-    for (void * p : {(void *) rc_tok_h, (void *) rc_dig_h, (void *) rc_forced_h})
-        if (p) (void) hipHostFree(p);
-    rc_tok_d = tok_dn; rc_tok_h = tok_hn;
-    rc_dig_d = dig_dn; rc_dig_h = dig_hn;
-    rc_forced_d = for_dn; rc_forced_h = for_hn;
-    rc_ctl_d = ctl_dn; rc_ctl_h = ctl_hn;
-    rc_cap = cap;
-    fresh.dev.clear();
-    fresh.host.clear();
-}
-
-// n_steps batched decode steps in one call (lvk_decode_batch_chain): step i evaluates, for every
-// row r, token t_i[r] at pos[r] + i on slot seqs[r], as decode_rows would with those n rows;
-// t_0[r] = forced[r], t_{i+1}[r] = forced[(i + 1) * n + r] while i + 1 < n_forced, else the argmax
-// of row r's logits of step i.  The host sets the rows, the forced table and the first embedding
-// rows up once; each step is the rows' forward pass followed by k_rows_step, which leaves x and
-// rows_d as the next step reads them.  The rows path of enqueue_forward takes positions and slots
-// from rows_d / slots_d alone (sp_d is read only by the fused QKV epilogues, which a rows step
-// does not run), so the step block needs no advancing on the device.  The steps are replays of
-// one captured graph, or the same launches enqueued eagerly when the graph is off or the
-// profiler is on.  Every argument is checked before anything is enqueued; the slots' counts move
-// only after the last step has completed.
-void Context::decode_rows_chain(const int * forced, int n_forced, const int * seqs, const int * pos, int n, int n_steps,
-                                int * out_tokens, unsigned long long * out_digests, float * logits_out) {
-    const HParams & hp = model.hp;
-    const int V = (int) hp.n_vocab, E = (int) hp.n_embd;
-    if (!slots_d) seq_init(1);
-    if (!forced || !seqs || !pos || !out_tokens) throw Error("lvk_decode_batch_chain: null argument");
-    if (n < 1 || n > n_ctx_user) throw Error("lvk_decode_batch_chain: the row count must be in 1..n_ctx");
-    if (n_steps < 1 || n_steps > n_ctx_user) throw Error("lvk_decode_batch_chain: n_steps must be in 1..n_ctx");
-    if (n_forced < 1 || n_forced > n_steps) throw Error("lvk_decode_batch_chain: n_forced must be in 1..n_steps");
-    std::vector<char> named((size_t) seq_count(), 0);
-    for (int r = 0; r < n; ++r) {
-        if (seqs[r] < 0 || seqs[r] >= seq_count()) throw Error("lvk_decode_batch_chain: sequence id out of range");
-        if (named[(size_t) seqs[r]]) throw Error("lvk_decode_batch_chain: a sequence may have one row only");
-        named[(size_t) seqs[r]] = 1;
-        if (pos[r] < 0 || pos[r] > seq_n(seqs[r]))
-            throw Error("lvk_decode_batch_chain: position past the end of its sequence (a hole)");
-        if (pos[r] > n_ctx_user - n_steps) throw Error("lvk_decode_batch_chain: pos + n_steps exceeds n_ctx");
-    }
-    const size_t nf = (size_t) n_forced * n, total = (size_t) n_steps * n;
-    for (size_t k = 0; k < nf; ++k)
-        if (forced[k] < 0 || forced[k] >= V) throw Error("lvk_decode_batch_chain: token id out of range");
-    rows_chain_reserve(total);
-    auto step = [&] {
-        enqueue_forward(n, false, tok_d, 0, true, /*embed=*/false, /*rows=*/true);
-        LVK_HIP(launch_rows_step(logits_d, V, n, rows_d, rc_ctl_d + 2, rc_ctl_d, rc_forced_d, rc_tok_d, rc_dig_d, nullptr,
-                                 model.tok_emb, model.emb_type, E, x, stream));
-    };
-    try {
-        if (sp_next > n_ctx) throw Error("llama.vk_amd: too many slices before a sync");
-        StepParams * sh = sp_h + sp_next++;
-        sh->n_past = 0;             // no kernel of this path takes a position from the step block
-        sh->n_tokens = n;
-        sh->pad0 = 0;
-        sh->seq = next_seq((unsigned) n_steps);
-        rc_ctl_h[0] = n_forced;
-        rc_ctl_h[1] = out_digests ? 1 : 0;
-        for (int r = 0; r < n; ++r) {
-            rows_h[r] = {seqs[r], pos[r]};
-            rc_ctl_h[2 + r] = pos[r];
-        }
-        std::memcpy(rc_forced_h, forced, sizeof(int) * nf);
-        LVK_HIP(hipMemcpyAsync(sp_d, sh, sizeof(StepParams), hipMemcpyHostToDevice, stream));
-        LVK_HIP(hipMemcpyAsync(rows_d, rows_h, sizeof(SeqRow) * (size_t) n, hipMemcpyHostToDevice, stream));
-        LVK_HIP(hipMemcpyAsync(rc_ctl_d, rc_ctl_h, sizeof(int) * (2 + (size_t) n), hipMemcpyHostToDevice, stream));
-        LVK_HIP(hipMemcpyAsync(rc_forced_d, rc_forced_h, sizeof(int) * nf, hipMemcpyHostToDevice, stream));
-        LVK_HIP(launch_embed(model.tok_emb, model.emb_type, E, rc_forced_d, n, x, stream));
-        if (use_graph && !profiling) {
-            // the row count (and the matmul path it selects) is baked into the graph's launches
-            if (graph_rows_exec && (graph_rows_n != n || graph_rows_exact != prompt_exact)) drop_rows_graph();
-            if (!graph_rows_exec) {
-                LVK_HIP(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-                try {
-                    step();
-                } catch (...) {
-                    hipGraph_t g = nullptr;
-                    (void) hipStreamEndCapture(stream, &g);
-                    if (g) (void) hipGraphDestroy(g);
-                    throw;
-                }
-                LVK_HIP(hipStreamEndCapture(stream, &graph_rows));
-                const hipError_t e = hipGraphInstantiate(&graph_rows_exec, graph_rows, nullptr, nullptr, 0);
-                if (e != hipSuccess) {
-                    graph_rows_exec = nullptr;
-                    drop_rows_graph();
-                    LVK_HIP(e);
-                }
-                graph_rows_n = n;
-                graph_rows_exact = prompt_exact;
-            }
-            for (int i = 0; i < n_steps; ++i) LVK_HIP(hipGraphLaunch(graph_rows_exec, stream));
-        } else {
-            for (int i = 0; i < n_steps; ++i) step();
-        }
-        LVK_HIP(hipMemcpyAsync(rc_tok_h, rc_tok_d, sizeof(int) * total, hipMemcpyDeviceToHost, stream));
-        if (out_digests) LVK_HIP(hipMemcpyAsync(rc_dig_h, rc_dig_d, 8 * total, hipMemcpyDeviceToHost, stream));
-        if (logits_out)
-            LVK_HIP(hipMemcpyAsync(logits_out, logits_d, sizeof(float) * (size_t) n * V, hipMemcpyDeviceToHost, stream));
-    } catch (...) {
-        (void) hipStreamSynchronize(stream);
-        sp_next = 1;
-        throw;
-    }
-    // the host logits of llama_get_logits are an earlier eval's: they stay as they are
-    const bool valid = logits_valid;
-    end_eval(true);
-    logits_valid = valid;
-    std::memcpy(out_tokens, rc_tok_h, sizeof(int) * total);
-    if (out_digests) std::memcpy(out_digests, rc_dig_h, 8 * total);
-    for (int r = 0; r < n; ++r) seq_n(seqs[r]) = pos[r] + n_steps;
-}
-
-}  // namespace lvk
-
-namespace lvk {
 // pipeline stages: the residual stream crosses stage boundaries
 void Context::x_copy(void * buf, int n, bool to_ctx, bool on_device) {
     if (n <= 0 || n > n_ctx) throw Error("llama.vk_amd: bad token count for the stage residual stream");

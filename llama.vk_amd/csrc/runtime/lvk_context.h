@@ -1,13 +1,12 @@
 // lvk_context.h -- one inference context: device KV cache, scratch, the
 // launch sequence of llama_eval on a HIP stream and the captured decode graph.
 #pragma once
-#include "lvk_model.h"
+#include "lvk_buffers.h"
 
 #include <array>
 #include <chrono>
 #include <functional>
 #include <memory>
-#include <new>
 
 struct llama_context_params;
 struct lvk_row_sample;      // include/lvk_ops.h
@@ -21,26 +20,6 @@ struct StageLinkDel { void operator()(StageLink * p) const; };
 
 // kernel classes timed by the profiler (events around every launch of a class)
 enum KClass : int { K_EMBED = 0, K_QKV, K_ATTN, K_WO, K_W13, K_W2, K_LMHEAD, K_NCLASS };
-
-// page-locked host storage: the per-token logits D2H copy runs as one DMA instead of
-// being staged through a driver bounce buffer
-template <class T>
-struct PinnedAlloc {
-    using value_type = T;
-    PinnedAlloc() = default;
-    template <class U>
-    PinnedAlloc(const PinnedAlloc<U> &) {}
-    T * allocate(size_t n) {
-        void * p = nullptr;
-        if (hipHostMalloc(&p, n * sizeof(T), hipHostMallocDefault) != hipSuccess) throw std::bad_alloc();
-        return (T *) p;
-    }
-    void deallocate(T * p, size_t) { (void) hipHostFree(p); }
-    template <class U>
-    bool operator==(const PinnedAlloc<U> &) const { return true; }
-    template <class U>
-    bool operator!=(const PinnedAlloc<U> &) const { return false; }
-};
 
 struct Profile {
     std::array<double, K_NCLASS> ms{};       // accumulated device time
@@ -65,7 +44,10 @@ struct Context {
     int n_ctx_user = 512;        // llama_context_params.n_ctx: the positions an eval may use
     bool logits_all = false;
     bool want_embedding = false;
-    hipStream_t stream = nullptr;
+    // destruction runs upwards: the graphs, events and buffers below go first, then the stream,
+    // then the stage link, and the model (whose arena holds the raw pointers below) last
+    std::unique_ptr<StageLink, StageLinkDel> link;   // one-stage-per-process link (lvk_stage_connect[_shm])
+    Stream stream;
 
     // device state
     uint16_t * kc = nullptr;     // [L][n_ctx][E] f16, or f32 when kv32
@@ -88,13 +70,12 @@ struct Context {
     float2 * rope = nullptr;     // [n_ctx][hd/2]
     StepParams * sp_d = nullptr;
     int * tok_d = nullptr;       // [n_ctx]
-    StepParams * sp_h = nullptr; // pinned, [1 + n_ctx] step blocks: [0] for the graphs, the
+    HostPtr<StepParams> sp_h;    // pinned, [1 + n_ctx] step blocks: [0] for the graphs, the
     int sp_next = 1;             //   rest one per eager slice enqueued before the next sync
-    int * tok_h = nullptr;       // pinned [n_ctx]
-    unsigned * err_h = nullptr;  // pinned, mapped: the kernels' error word (lvk_kernels.h DevError)
+    HostPtr<int> tok_h;          // pinned [n_ctx]
+    HostPtr<unsigned> err_h;     // host-mapped: the kernels' error word (lvk_kernels.h DevError)
     unsigned * err_d = nullptr;  // its device address
     int device = 0;              // the HIP device of this context
-    std::unique_ptr<StageLink, StageLinkDel> link;   // one-stage-per-process link (lvk_stage_connect[_shm])
 
     // prompt (N > 1) path: MFMA matmuls with exact block dots (default) or the
     // bit-faithful VALU kernels (prompt_exact; env LVK_PROMPT_EXACT=1)
@@ -116,20 +97,19 @@ struct Context {
     // quantized aq_attn
     float * attn_f32 = nullptr;  // [C][E]
 
-    // decode graph (N = 1, last-token logits)
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t graph_exec = nullptr;
+    // the single-token decode graphs, captured on first use (build_graph):
+    //   LOGITS  last-token logits (llama_eval)
+    //   GREEDY  lvk_eval_greedy: argmax on the device, 4-byte D2H instead of the logits row
+    //   SAMPLE  lvk_eval_sample: the sampler block H2D, the forward pass and the device top-k
+    //           candidates (sample.hip) into host-mapped memory instead of the logits row
+    //   CHAIN   one step of lvk_decode_greedy (below)
+    enum class DecodeGraph { LOGITS, GREEDY, SAMPLE, CHAIN };
+    std::array<Graph, 4> graphs;
+    Graph & graph_of(DecodeGraph k) { return graphs[(size_t) k]; }
     bool use_graph = true;
-    // greedy decode graph (lvk_eval_greedy): argmax on the device, 4-byte D2H instead of the logits row
-    hipGraph_t graph_greedy = nullptr;
-    hipGraphExec_t graph_greedy_exec = nullptr;
-    // sampling decode graph (lvk_eval_sample): the sampler block H2D, the forward pass and the
-    // device top-k candidates (sample.hip) into host-mapped memory instead of the logits row
-    hipGraph_t graph_sample = nullptr;
-    hipGraphExec_t graph_sample_exec = nullptr;
-    SampleParams * samp_h = nullptr;   // pinned host block, filled per call
+    HostPtr<SampleParams> samp_h;      // pinned host block, filled per call
     SampleParams * samp_d = nullptr;
-    SampleOut * sout_h = nullptr;      // host-mapped candidates
+    HostPtr<SampleOut> sout_h;         // host-mapped candidates
     SampleOut * sout_d = nullptr;      // its device address
     // one single-token eval + the device half of the sampler (samp_h filled by the caller);
     // the candidates are in *sout_h afterwards
@@ -138,21 +118,19 @@ struct Context {
     void fetch_logits();
     int n_sample_fallback = 0;         // lvk_eval_sample calls / lvk_decode_batch_sample rows that took the all-logits host path
     int * greedy_d = nullptr;
-    int * greedy_h = nullptr;    // host-mapped (coherent): the device argmax writes it
+    HostPtr<int> greedy_h;       // host-mapped (coherent): the device argmax writes it
     int * greedy_hd = nullptr;   // its device address
     void enqueue_argmax();
     // chained greedy decode (lvk_decode_greedy): one graph per step that reads nothing from
     // the host -- its last kernel (k_argmax_step) picks the token, advances the step block
     // on the device and writes the next step's embedding row -- replayed n times per call
-    hipGraph_t graph_chain = nullptr;
-    hipGraphExec_t graph_chain_exec = nullptr;
     int * chain_d = nullptr;     // [CHAIN_HDR + n_ctx]: step counter, forced count, digest flag, pad; the argmax tokens
-    int * chain_h = nullptr;     // pinned copy of the tokens
-    int * chain_ctl_h = nullptr; // pinned header block (CHAIN_HDR ints)
+    HostPtr<int> chain_h;        // pinned copy of the tokens
+    HostPtr<int> chain_ctl_h;    // pinned header block (CHAIN_HDR ints)
     int * forced_d = nullptr;    // [n_ctx] teacher-forced tokens of a chained decode
-    int * forced_h = nullptr;    // pinned staging of them
+    HostPtr<int> forced_h;       // pinned staging of them
     unsigned long long * digest_d = nullptr;   // [n_ctx] per-step logits digests
-    unsigned long long * digest_h = nullptr;   // pinned copy
+    HostPtr<unsigned long long> digest_h;      // pinned copy
     int decode_chain(const int * tokens, int n_tokens, int n_past, int n_steps, int * out, unsigned long long * digests);
     // decode attention granule epochs from the step counter (StepParams::seq): no zeroing per
     // token (off for models with more than 126 layers)
@@ -163,17 +141,19 @@ struct Context {
     // batched decode (lvk_decode_batch): KV slots beside kc / vc, which are slot 0 with the count
     // kv_n.  seq_kv[s - 1] is slot s >= 1 in the same layout (f16, zeroed at allocation).
     struct SeqKV {
-        uint16_t * kc = nullptr;
-        uint16_t * vc = nullptr;
+        DevPtr<uint16_t> kc, vc;
         int n = 0;               // positions held
     };
     std::vector<SeqKV> seq_kv;
-    SeqSlot * slots_d = nullptr; // [seq_count()] base pointers of every slot (nullptr before seq_init)
-    SeqRow * rows_d = nullptr;   // [n_ctx] {slot, pos} of a call's rows
-    SeqRow * rows_h = nullptr;   // pinned staging of them
-    int * amax_d = nullptr;      // [n_ctx] per-row argmax
+    DevPtr<SeqSlot> slots_d;     // [seq_count()] base pointers of every slot (empty before seq_init)
+    DevPtr<SeqRow> rows_d;       // [n_ctx] {slot, pos} of a call's rows
+    HostPtr<SeqRow> rows_h;      // pinned staging of them
+    DevPtr<int> amax_d;          // [n_ctx] per-row argmax
     int seq_count() const { return 1 + (int) seq_kv.size(); }
     int & seq_n(int s) { return s == 0 ? kv_n : seq_kv[(size_t) s - 1].n; }
+    SeqSlot slot_kv(int s) const {      // the K and V of slot s >= 0
+        return s == 0 ? SeqSlot{kc, vc} : SeqSlot{seq_kv[(size_t) s - 1].kc.get(), seq_kv[(size_t) s - 1].vc.get()};
+    }
     // allocate slots up to n_seq (fewer than now: nothing); on failure nothing has changed
     void seq_init(int n_seq);
     void seq_copy(int dst, int src, int n_tokens);
@@ -184,11 +164,13 @@ struct Context {
     void decode_rows_chain(const int * forced, int n_forced, const int * seqs, const int * pos, int n, int n_steps,
                            int * out_tokens, unsigned long long * out_digests, float * logits_out);
     void rows_chain_reserve(size_t entries);
-    void drop_rows_graph();
-    // decode_rows' step, then per row with rows[i].sample != 0 the sampler on row i's logits
-    // (lvk_decode_batch_sample): greedy rows through launch_argmax_rows, the others through one
-    // launch_sample_cand_rows and the host tail of lvk_eval_sample per row, in row order, drawing
-    // from the row's slot's generator
+    // what the three decode_rows* share: rows_begin takes a step slice, fills its block (pad0 as
+    // given) and stages and copies the block, the tokens (nullptr: none) and the rows; rows_finish
+    // ends the step with the host logits of llama_get_logits left as they were (an earlier eval's)
+    void rows_begin(const int * tokens, const int * seqs, const int * pos, int n, int pad0, unsigned n_seq = 1);
+    void rows_finish(const std::vector<int> & next);      // next: rows_check's, the slots' new counts
+    // decode_rows' step, then per row with rows[i].sample != 0 the sampler on row i's logits,
+    // drawing from the row's slot's generator (lvk_decode_batch_sample; lvk_rows.cpp has the paths)
     void decode_rows_sample(const int * tokens, const int * seqs, const int * pos, int n, const lvk_row_sample * rows,
                             int * out_tokens);
     // the checks of a batched decode step's rows; next[s]: the count slot s has after the step (-1: no row)
@@ -196,9 +178,12 @@ struct Context {
     // per sampled row of a step (sr_cap of them, grown on demand): the candidates (host-mapped)
     // and the kernel's record; sr_pool_cap ints of last-n windows back to back
     size_t sr_cap = 0, sr_pool_cap = 0;
-    SampleOut * sr_out_h = nullptr, * sr_out_d = nullptr;
-    SampleRow * sr_rec_h = nullptr, * sr_rec_d = nullptr;   // pinned staging, device
-    int * sr_pool_h = nullptr, * sr_pool_d = nullptr;
+    HostPtr<SampleOut> sr_out_h;        // host-mapped
+    SampleOut * sr_out_d = nullptr;     // its device address
+    HostPtr<SampleRow> sr_rec_h;        // pinned staging
+    DevPtr<SampleRow> sr_rec_d;
+    HostPtr<int> sr_pool_h;
+    DevPtr<int> sr_pool_d;
     void rows_sample_reserve(size_t rows, size_t pool);
     // the generators of slots >= 1 (slot 0 draws from rng), seeded with `seed` at seq_init
     std::vector<std::mt19937> seq_rng;
@@ -221,11 +206,10 @@ struct Context {
     // profiling
     bool profiling = false;
     Profile prof;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
+    std::vector<std::pair<Event, Event>> ev_pool;
     std::vector<int> ev_class;
     size_t ev_used = 0;
 
-    ~Context();
     void init(const llama_context_params & p);
     void eval(const int * tokens, int n, int n_past);
     // eval = begin_eval (everything enqueued on `stream`, no host wait) + end_eval (sync,
@@ -233,19 +217,47 @@ struct Context {
     // with the residual-stream hand-offs and ends them together
     void begin_eval(const int * tokens, int n, int n_past, const EvalPart & part);
     void begin_eval_safe(const int * tokens, int n, int n_past, const EvalPart & part);
+    // run fn; if it throws, the work already queued drains before the error propagates, with the
+    // step slices released (reset_slices) and the host logits marked stale (stale_logits) as asked
+    template <class F> void drain_on_error(bool reset_slices, bool stale_logits, F && fn) {
+        try {
+            fn();
+        } catch (...) {
+            (void) hipStreamSynchronize(stream);
+            if (reset_slices) sp_next = 1;
+            if (stale_logits) logits_valid = false;
+            throw;
+        }
+    }
     void end_eval(bool no_host_logits);
     // stage boundary: copy the residual stream x [n][E] to (to_ctx) or from the context
     void x_copy(void * buf, int n, bool to_ctx, bool on_device);
-    // rows: the n tokens are the rows of a batched decode step (rows_d / slots_d) instead of n
-    // consecutive positions of slot 0
-    void enqueue_forward(int n, bool last_only, const int * tok_src = nullptr, int logit_row = 0, bool head = true,
-                         bool embed = true, bool rows = false);
+    struct Forward {
+        int n = 1;                      // tokens
+        bool last_only = true;          // lm_head over the last token only
+        const int * tok_src = nullptr;  // device tokens of the embedding (nullptr: tok_d)
+        int logit_row = 0;              // first row of logits_d written
+        bool head = true;               // run norm + lm_head
+        bool embed = true;              // run the embedding (false: x holds the rows already)
+        bool rows = false;              // the tokens are a batched decode step's rows (rows_d / slots_d), not
+                                        //   n consecutive positions of slot 0
+    };
+    static Forward rows_forward(int n) {      // a batched decode step over n rows, every row's logits
+        Forward f;
+        f.n = n;
+        f.last_only = false;
+        f.rows = true;
+        return f;
+    }
+    void enqueue_forward(const Forward & f);
     bool use_batched(int n) const;
-    void build_graph(int kind = 0);      // 0 logits, 1 greedy, 2 sample, 3 chained greedy step
+    void build_graph(DecodeGraph kind);
     int eval_greedy(int token, int n_past);
     void kv_get();
     void kv_set(const uint8_t * src, size_t n);
     void kv_copy_from(const Context & src, int n_tokens);
+    // positions [0, n_tokens) of every layer's K and V, device to device, then a stream sync
+    void copy_kv_prefix(uint16_t * dk, uint16_t * dv, const uint16_t * sk, const uint16_t * sv, int n_tokens);
     size_t kv_bytes() const;
     void timed_launch(int cls, double bytes, const std::function<hipError_t()> & fn);
     void collect_profile();
@@ -255,17 +267,16 @@ struct Context {
     // chained batched decode (lvk_decode_batch_chain): one graph per step of n rows that reads
     // nothing from the host -- the rows' forward pass, then k_rows_step, which picks every row's
     // next token, writes its embedding row and advances rows_d -- replayed n_steps times per call
-    hipGraph_t graph_rows = nullptr;
-    hipGraphExec_t graph_rows_exec = nullptr;
-    int graph_rows_n = 0;            // the row count baked into the graph's launches
-    bool graph_rows_exact = false;   // prompt_exact at capture (it selects the matmul path)
+    Graph graph_rows;
+    int graph_rows_n = 0;            // its key: the row count baked into the graph's launches
+    bool graph_rows_exact = false;   //   and prompt_exact at capture (it selects the matmul path)
     // per call: [n_steps][n] argmax tokens and digests, [n_forced][n] forced tokens (rc_cap
     // entries each, grown on demand), the rows' start positions and {n_forced, digest flag}
     size_t rc_cap = 0;
-    int * rc_tok_d = nullptr, * rc_tok_h = nullptr;
-    unsigned long long * rc_dig_d = nullptr, * rc_dig_h = nullptr;
-    int * rc_forced_d = nullptr, * rc_forced_h = nullptr;
-    int * rc_ctl_d = nullptr, * rc_ctl_h = nullptr;       // [2 + n_ctx]: the two control words, then the start positions
+    DevPtr<int> rc_tok_d, rc_forced_d, rc_ctl_d;          // rc_ctl: [2 + n_ctx], the two control words, then the
+    HostPtr<int> rc_tok_h, rc_forced_h, rc_ctl_h;         //   start positions; allocated once
+    DevPtr<unsigned long long> rc_dig_d;
+    HostPtr<unsigned long long> rc_dig_h;
 };
 
 int64_t now_us();

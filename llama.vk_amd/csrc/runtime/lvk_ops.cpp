@@ -14,22 +14,6 @@
 
 namespace {
 
-struct Dev {
-    std::vector<void *> ptrs;
-    void * get(size_t n) {
-        void * p = nullptr;
-        LVK_HIP(hipMalloc(&p, n ? n : 16));
-        ptrs.push_back(p);
-        return p;
-    }
-    template <class T> T * up(const T * h, size_t n) {
-        T * d = (T *) get(n * sizeof(T));
-        LVK_HIP(hipMemcpy(d, h, n * sizeof(T), hipMemcpyHostToDevice));
-        return d;
-    }
-    ~Dev() { for (void * p : ptrs) (void) hipFree(p); }
-};
-
 int fail(const char * fn, const std::string & m) {
     fprintf(stderr, "%s: %s\n", fn, m.c_str());
     return -1;
@@ -40,7 +24,7 @@ size_t block_bytes(int type) { return type == lvk::Q4_0 ? 20 : 24; }
 __attribute__((target("f16c"))) uint16_t h_f32_to_f16(float f) { return _cvtss_sh(f, 0); }
 
 // device arrays of a quantized activation: n rows of nb blocks
-lvk::ActQ actq_alloc(Dev & dv, size_t n, size_t nb) {
+lvk::ActQ actq_alloc(lvk::Scratch & dv, size_t n, size_t nb) {
     lvk::ActQ q;
     q.nb = (int) nb;
     q.d = (float *) dv.get(n * nb * 4);
@@ -82,7 +66,7 @@ const char * lvk_version(void) { return "llama.vk_amd 0.1 (gfx950)"; }
 int lvk_quantize_rows(int type, const float * x, int n, int k, void * y) {
     try {
         if (k % 32) return fail(__func__, "k must be a multiple of 32");
-        Dev dv;
+        lvk::Scratch dv;
         const size_t nb = (size_t) k / 32;
         float * xd = dv.up(x, (size_t) n * k);
         const lvk::ActQ q = actq_alloc(dv, (size_t) n, nb);
@@ -95,7 +79,7 @@ int lvk_quantize_rows(int type, const float * x, int n, int k, void * y) {
 static int mul_mat_impl(int type, const void * w, int m, int k, const float * g, const float * x, int n, float * y,
                         bool norm) {
     if (m % 8 || k % 256) return fail("lvk_mul_mat_q", "need m % 8 == 0 and k % 256 == 0");
-    Dev dv;
+    lvk::Scratch dv;
     const size_t nb = (size_t) k / 32, bb = block_bytes(type);
     void * wd = dv.up((const uint8_t *) w, (size_t) m * nb * bb);
     lvk::QMatrix q;
@@ -140,7 +124,7 @@ int lvk_mul_mat_q_norm(int type, const void * w, int m, int k, const float * g, 
 }
 
 // y[n][M] = W . act(x) through the batched interface: operand image (xm zeroed once), then the matmul
-static void mm_batched(Dev & dv, const lvk::QMatrix & q, const float * xd, const float * gd, int n, float * yd) {
+static void mm_batched(lvk::Scratch & dv, const lvk::QMatrix & q, const float * xd, const float * gd, int n, float * yd) {
     const lvk::ActImageBytes nbytes = lvk::act_image_bytes(q.qtype, n, q.K);
     lvk::MmLaunch L;
     L.w = q; L.N = n; L.y = yd; L.ldy = q.M;
@@ -160,7 +144,7 @@ int lvk_mul_mat_q_mfma(int type, const void * w, int m, int k, const float * g, 
     try {
         if (type != lvk::Q4_0 && type != lvk::Q4_1) return fail(__func__, "Q4_0 / Q4_1 only");
         if (m % 128 || k % 256 || n < 1) return fail(__func__, "need m % 128 == 0, k % 256 == 0, n >= 1");
-        Dev dv;
+        lvk::Scratch dv;
         const size_t nb = (size_t) k / 32;
         void * wd = dv.up((const uint8_t *) w, (size_t) m * nb * (type == lvk::Q4_0 ? 20 : 24));
         lvk::QMatrix q;
@@ -190,7 +174,7 @@ int lvk_mul_mat_f16(const uint16_t * w, int m, int k, const float * g, const flo
         if (!w || !x || !y || m < 1 || n < 1 || k < 256 || k % 256) return fail(__func__, "need m >= 1, n >= 1, k % 256 == 0");
         if (kernel < 0 || kernel > 2 || (kernel == 1 && n != 1)) return fail(__func__, "kernel: 0 auto, 1 decode matvec (n == 1), 2 batched");
         if (kernel == 0) kernel = n == 1 ? 1 : 2;
-        Dev dv;
+        lvk::Scratch dv;
         const uint16_t * wd = dv.up(w, (size_t) m * k);
         lvk::QMatrix q;
         q.qtype = lvk::F16; q.M = m; q.K = k;
@@ -217,7 +201,7 @@ int lvk_mul_mat_f32(const float * w, int m, int k, const float * g, const float 
         if (!w || !x || !y || m < 1 || n < 1 || k < 256 || k % 256) return fail(__func__, "need m >= 1, n >= 1, k % 256 == 0");
         if (kernel < 0 || kernel > 2 || (kernel == 1 && n != 1)) return fail(__func__, "kernel: 0 auto, 1 decode matvec (n == 1), 2 batched");
         if (kernel == 0) kernel = n == 1 ? 1 : 2;
-        Dev dv;
+        lvk::Scratch dv;
         const float * wd = dv.up(w, (size_t) m * k);
         lvk::QMatrix q;
         q.qtype = lvk::F32; q.M = m; q.K = k;
@@ -293,7 +277,7 @@ static int attention_impl(const uint16_t * kc, const uint16_t * vc, const float 
                           void * blocks) {
     const char * fn = kind == 1 ? "lvk_attention_prompt" : kind == 2 ? "lvk_attention_decode" : "lvk_attention";
     try {
-        Dev dv;
+        lvk::Scratch dv;
         const size_t CE = (size_t) n_ctx * n_embd;
         std::vector<uint16_t> q16((size_t) n * n_embd);
         for (size_t i = 0; i < q16.size(); ++i) q16[i] = h_f32_to_f16(q[i]);   // ggml.c:6420-6433
@@ -360,7 +344,7 @@ struct RowsDev {
     lvk::SeqRow * rows;
     size_t layer_off, total;
 };
-RowsDev rows_upload(Dev & dv, const uint16_t * kc, const uint16_t * vc, const int * slots, const int * pos, int n,
+RowsDev rows_upload(lvk::Scratch & dv, const uint16_t * kc, const uint16_t * vc, const int * slots, const int * pos, int n,
                     int n_embd, int n_ctx, int n_slots, int n_layer, int layer) {
     const size_t CE = (size_t) n_ctx * n_embd;
     RowsDev r;
@@ -385,7 +369,7 @@ int lvk_rope_kv_rows(const float * qkv, const int * slots, const int * pos, int 
         if (!qkv || !kc || !vc || !q16_out) return fail(__func__, "null argument");
         if (const char * bad = rows_args_bad(slots, pos, n, n_embd, n_head, n_ctx, n_slots, n_layer, layer))
             return fail(__func__, bad);
-        Dev dv;
+        lvk::Scratch dv;
         const int hd = n_embd / n_head;
         const RowsDev r = rows_upload(dv, kc, vc, slots, pos, n, n_embd, n_ctx, n_slots, n_layer, layer);
         std::vector<float2> rt;
@@ -409,7 +393,7 @@ int lvk_attention_rows(int type, const uint16_t * kc, const uint16_t * vc, int n
         if (type != lvk::Q4_0 && type != lvk::Q4_1) return fail(__func__, "type: 2 (Q4_0) or 3 (Q4_1)");
         if (const char * bad = rows_args_bad(slots, pos, n, n_embd, n_head, n_ctx, n_slots, n_layer, layer))
             return fail(__func__, bad);
-        Dev dv;
+        lvk::Scratch dv;
         const RowsDev r = rows_upload(dv, kc, vc, slots, pos, n, n_embd, n_ctx, n_slots, n_layer, layer);
         std::vector<uint16_t> q16((size_t) n * n_embd);
         for (size_t i = 0; i < q16.size(); ++i) q16[i] = h_f32_to_f16(q[i]);   // ggml.c:6420-6433
@@ -433,7 +417,7 @@ int lvk_attention_rows(int type, const uint16_t * kc, const uint16_t * vc, int n
 
 int lvk_exp_table_mismatches(void) {
     try {
-        Dev dv;
+        lvk::Scratch dv;
         std::vector<uint16_t> te, ts;
         lvk::host_fp16_tables(te, ts);
         const uint16_t * tab = dv.up(te.data(), te.size());
@@ -449,7 +433,7 @@ int lvk_exp_table_mismatches(void) {
 
 int lvk_rms_norm_mul(const float * x, const float * g, int k, int n, float * y) {
     try {
-        Dev dv;
+        lvk::Scratch dv;
         float * xd = dv.up(x, (size_t) n * k);
         float * gd = dv.up(g, (size_t) k);
         float * yd = (float *) dv.get((size_t) n * k * 4);
@@ -600,7 +584,7 @@ int lvk_sample_candidates_rows(const float * x, int n_rows, int n, const int * s
                 throw lvk::Error("arguments out of range");
             rec[(size_t) j] = {sel[j], k[j], nl, last_off[j], 1.0f / temp[j], rp[j]};
         }
-        Dev dv;
+        lvk::Scratch dv;
         float * xd = dv.up(x, (size_t) n_rows * n);
         lvk::SampleRow * rd = dv.up(rec.data(), rec.size());
         const size_t n_pool = (size_t) last_off[n_sel];
@@ -628,7 +612,7 @@ int lvk_rows_step(const float * logits, int n, int V, const int * forced, int n_
             (n_forced > 0 && !forced) || (size_t) n * ((size_t) step + 1) > ((size_t) 1 << 24) ||
             (size_t) n * (size_t) n_forced > ((size_t) 1 << 24))
             throw lvk::Error("arguments out of range");
-        Dev dv;
+        lvk::Scratch dv;
         const size_t total = (size_t) n * ((size_t) step + 1), off = (size_t) n * (size_t) step;
         float * xd = dv.up(logits, (size_t) n * V);
         std::vector<lvk::SeqRow> rows((size_t) n, lvk::SeqRow{0, step});
@@ -652,7 +636,7 @@ int lvk_rows_step(const float * logits, int n, int V, const int * forced, int n_
 int lvk_argmax(const float * x, int n) {
     try {
         if (n <= 0) throw lvk::Error("n must be positive");
-        Dev dv;
+        lvk::Scratch dv;
         float * xd = dv.up(x, (size_t) n);
         int * od = (int *) dv.get(4);
         int r = -1;
@@ -668,7 +652,7 @@ int lvk_sample_candidates(const float * x, int n, const int * last, int n_last, 
         if (n <= 0 || n > lvk::SAMPLE_MAX_VOCAB || k < 1 || k > std::min(n, lvk::SAMPLE_CAP) || temp <= 0 ||
             n_last < 0 || n_last > lvk::SAMPLE_MAX_LAST || (n_last > 0 && !last))
             throw lvk::Error("arguments out of range");
-        Dev dv;
+        lvk::Scratch dv;
         float * xd = dv.up(x, (size_t) n);
         lvk::SampleParams p{};
         p.k = k;
@@ -698,7 +682,7 @@ int lvk_eval_greedy(struct llama_context * ctx, int token, int n_past) {
         if (ctx->split) {
             ctx->split->eval(&token, 1, n_past, true);
             c.kv_n = n_past + 1;
-            r = *c.greedy_h;
+            r = c.greedy_h[0];
         } else {
             r = c.eval_greedy(token, n_past);
         }

@@ -574,7 +574,7 @@ int stage_step(Context & c, const int * tokens, int n, int n_past, bool greedy, 
             if (s == S - 1) T.send(c.greedy_d, sizeof(int), 0, c.stream);
             if (s == 0) {
                 T.recv(c.greedy_d, sizeof(int), S - 1, c.stream);
-                LVK_HIP(hipMemcpyAsync(c.greedy_h, c.greedy_d, sizeof(int), hipMemcpyDeviceToHost, c.stream));
+                LVK_HIP(hipMemcpyAsync(c.greedy_h.get(), c.greedy_d, sizeof(int), hipMemcpyDeviceToHost, c.stream));
             }
         }
         T.wait(c.stream);
@@ -592,7 +592,7 @@ int stage_step(Context & c, const int * tokens, int n, int n_past, bool greedy, 
         c.logits_valid = false;
         throw Error(err);
     }
-    return greedy && (s == 0 || s == S - 1) ? *c.greedy_h : 0;
+    return greedy && (s == 0 || s == S - 1) ? c.greedy_h[0] : 0;
 }
 
 }  // namespace lvk

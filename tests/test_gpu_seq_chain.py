@@ -205,6 +205,31 @@ def test_row_count_change_seq_init_and_graph_off(lvk, models):
     h.close()
 
 
+def test_step_buffers_regrown_between_calls(lvk, models):
+    """three calls of 3 rows on one context of n_ctx 128: 8 steps, then 60 (180 entries, past the
+    first reserve of 128: the step outputs are replaced by larger buffers and the step graph, which
+    held the old addresses, is captured again), then 8 on the grown buffers.  Tokens, digests and
+    last logits of every call equal the host-fed loop on a second context"""
+    from oracle_lib import forced_tokens
+    path = models["tiny_q4_0"]
+    m, h = lvk.Llama(path, n_ctx=128), lvk.Llama(path, n_ctx=128)
+    for c in (m, h):
+        c.seq_init(3)
+    seqs, pos = [0, 1, 2], [0, 0, 0]
+    for k, steps in enumerate((8, 60, 8)):
+        forced = forced_tokens(3, seed=90 + k).reshape(1, 3)
+        got, dg, lg = m.decode_batch_chain(forced, seqs, pos, steps, digests=True, logits=True)
+        want, want_d, want_lg = host_loop(lvk, h, forced, seqs, pos, steps)
+        assert got.shape == (steps, 3), "call %d" % k
+        assert np.array_equal(got, want), "call %d: tokens" % k
+        assert np.array_equal(dg, want_d), "call %d: digests" % k
+        assert np.array_equal(bits(lg), bits(want_lg)), "call %d: last logits" % k
+        pos = [p + steps for p in pos]
+        assert [m.seq_tokens(s) for s in seqs] == pos
+    m.close()
+    h.close()
+
+
 def test_slot0_interop_and_default_context(lvk, models):
     """a chain that includes slot 0 leaves llama_get_kv_cache_token_count at its end, and the
     ordinary llama_eval continues from there; a context that never called seq_init chains on its

@@ -33,6 +33,7 @@ ROW_LENS = [6, 9, 13]
 ROW_SEED, ROW_STEPS = 3, 24
 BIG = dict(n_embd=4096, n_head=32, n_layer=2, ftype=2, seed=7)     # w4096_l2.bin, as test_gpu_sampling.py
 BIG_SEQS, BIG_STEPS, BIG_SEED = 16, 8, 1
+REGROW_SEQS, REGROW_SEED, REGROW_PROMPT_SEED = 20, 1, 170   # test_sampler_buffers_regrown_between_calls
 
 
 def prompt(n, seed):
@@ -213,6 +214,49 @@ def test_per_row_parameters_match_single_sequence_sampler(lvk, tiny_models, name
         assert sq.out[i] == replay(r, ROW_SEED, p, ROW_PARAMS[i], ROW_STEPS), "sequence %d" % i
     assert [m.seq_tokens(s) for s in (2, 0, 1)] == [n - 1 + ROW_STEPS for n in ROW_LENS]
     assert r.sample_fallbacks() == 0
+    m.close()
+    r.close()
+
+
+def regrow_prompts():
+    return [prompt(2 + s % 3, REGROW_PROMPT_SEED + s) for s in range(REGROW_SEQS)]
+
+
+def test_sampler_buffers_regrown_between_calls(lvk, tiny_models):
+    """three calls on one context: 2 device-sampled rows with 8-id windows, then 20 rows on 20
+    slots with 64-id windows (past the first reserve of 16 rows and 1024 pool ints: the records,
+    the candidates and the pool are replaced by larger buffers), then the first 2 rows again on
+    the grown buffers.  Every token equals the sequence alone through eval_sample with the same
+    seed, parameters and windows; no row took the all-logits path"""
+    path = tiny_models["tiny_q4_0"]
+    m = lvk.Llama(path, n_ctx=64, seed=REGROW_SEED)
+    m.seq_init(REGROW_SEQS)
+    r = lvk.Llama(path, n_ctx=64, seed=99)
+    toks = regrow_prompts()
+    pre = [(t, s, p) for s, pr in enumerate(toks) for p, t in enumerate(pr[:-1])]
+    m.decode_batch([a for a, _, _ in pre], [b for _, b, _ in pre], [c for _, _, c in pre], logits=False)
+    calls = [([0, 1], 8), (list(range(REGROW_SEQS)), 64), ([0, 1], 8)]
+    out = [[] for _ in toks]
+    for which, n_win in calls:
+        got = m.decode_batch_sample([toks[i][-1] for i in which], which, [len(toks[i]) - 1 for i in which],
+                                    [dict(SP, last_tokens=window(toks[i])[-n_win:]) for i in which])
+        for i, t in zip(which, got.tolist()):
+            toks[i].append(t)
+            out[i].append(t)
+    assert m.sample_fallbacks() == 0
+    for i, p in enumerate(regrow_prompts()):
+        # the sequence alone: slot 0 of r reseeded, the prompt token by token, then its draws
+        r.seq_seed(0, REGROW_SEED)
+        for pos, t in enumerate(p[:-1]):
+            r.eval([t], pos)
+        seq, want = list(p), []
+        for which, n_win in calls:
+            if i in which:
+                want.append(r.eval_sample(seq[-1], len(seq) - 1, window(seq)[-n_win:], **SP))
+                seq.append(want[-1])
+        assert out[i] == want, "sequence %d" % i
+    assert r.sample_fallbacks() == 0
+    assert [m.seq_tokens(s) for s in range(REGROW_SEQS)] == [len(t) - 1 for t in toks]
     m.close()
     r.close()
 
