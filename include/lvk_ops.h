@@ -318,6 +318,45 @@ LVK_API int lvk_sample_candidates_rows(const float * x, int n_rows, int n, const
                                        const float * temp, const float * rp, const int * last, const int * last_off,
                                        float * vals, int * ids, int * counts, int * flags);
 
+/* Scoring on the device: the probability of a given token per logits row, what perplexity, the
+ * log-likelihood of a continuation and multiple-choice evals need, without the [n][n_vocab] copy
+ * and the host softmax of the logits_all route (examples/perplexity/perplexity.cpp:6-20, 63-73).
+ *
+ * probs[i] = softmax(logits row i)[targets[i]] with the reference's arithmetic: the row maximum
+ * from logits[0] on by std::max's rule, e = expf(x - max) as a float, the sum of the e in
+ * double, (float) ((double) e_target / sum).  A row with targets[i] < 0 is not scored: probs[i] =
+ * -1.0f.  NaN anywhere in a row, a +inf maximum or an all -inf row give NaN; a target about 104 or
+ * more below the maximum gives 0, one between about 87.3 and 104 below it a denormal.
+ * lvk_score_host is that definition on the host, bit for bit the reference's result on this
+ * host (same operations, same order, this host's expf).  The device kernel (score.hip, one
+ * workgroup per row, the row read once) rounds a double-precision exp to float where the host
+ * calls expf and sums in a tree: a finite result is within 2 ulp of lvk_score_host's (distance of
+ * the floats' ordered integer representations, denormals included); 0, NaN and -1.0f match.
+ * argmax (optional, may be NULL): [n] ints, the first-maximum rule of lvk_decode_batch per row,
+ * unscored rows included.
+ *
+ * lvk_score_rows / lvk_score_host: op level on host arrays logits [n][V], n >= 1, every target
+ * < V.  lvk_score_rows takes 1 <= V <= 32768 (the row is held in registers); 0 / -1.
+ *
+ * lvk_eval_score is llama_eval(ctx, tokens, n_tokens, n_past, .) with the lm_head over every row,
+ * whatever the context's logits_all and f16_kv, ended by the score kernel over targets[n_tokens]:
+ * only probs (and argmax) cross PCIe.  The KV cache, its token count and the timings end as after
+ * that llama_eval.  Runs eagerly (no graph).  A model with n_vocab > 32768 takes lvk_score_host
+ * over the scored rows, copied to the host one by one.
+ * lvk_decode_batch_score is lvk_decode_batch(ctx, tokens, seqs, pos, n, NULL, NULL) ended by the
+ * score kernel, with that call's row rules, refusals and timings.
+ * Both check every argument before anything is enqueued (null pointers, the row count, token ids,
+ * every target < n_vocab): 0, or -1 with a message on stderr and the context and every slot
+ * unchanged.  Layer-split and stage contexts return -1.  llama_get_logits is NOT refreshed
+ * (after lvk_eval_score the host logits are stale, as after lvk_eval_greedy: llama_sample_top_p_top_k
+ * refuses them until the next llama_eval). */
+LVK_API int lvk_score_rows(const float * logits, int n, int V, const int * targets, float * probs, int * argmax);
+LVK_API int lvk_score_host(const float * logits, int n, int V, const int * targets, float * probs);
+LVK_API int lvk_eval_score(struct llama_context * ctx, const int * tokens, int n_tokens, int n_past,
+                           const int * targets, float * probs, int * argmax);
+LVK_API int lvk_decode_batch_score(struct llama_context * ctx, const int * tokens, const int * seqs, const int * pos,
+                                   int n, const int * targets, float * probs, int * argmax);
+
 /* Pipeline stages (the 65B layer split).  A stage context holds
  * layers [layer_begin, layer_end) of the model file (weights and KV cache); the
  * first stage (layer_begin == 0) also holds the token embeddings, the last one

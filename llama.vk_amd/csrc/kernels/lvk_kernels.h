@@ -427,6 +427,12 @@ hipError_t launch_argmax_step(const float * logits, int n, StepParams * sp, int 
 hipError_t launch_rows_step(const float * logits, int n_vocab, int n, SeqRow * rows, const int * pos0, const int * ctl,
                             const int * forced, int * out_tok, unsigned long long * digest, int * next_tok,
                             const void * emb, int emb_type, int n_embd, float * x, hipStream_t s);
+// the scoring tail (score.hip; lvk_eval_score, lvk_decode_batch_score): probs[i] = the reference's
+// softmax(logits[i])[targets[i]] (perplexity.cpp:6-20) for the n rows of logits [n][n_vocab], one
+// workgroup each; a row with targets[i] < 0 gets -1.0f.  Every other target must be < n_vocab (the
+// host checks it).  The row stays in registers: 1 <= n_vocab <= SCORE_MAX_VOCAB.
+constexpr int SCORE_MAX_VOCAB = 32768;
+hipError_t launch_score_rows(const float * logits, int n_vocab, int n, const int * targets, float * probs, hipStream_t s);
 
 // ---------------------------------------------------------------------------
 // ggml graph operators (graph_ops.hip; include/ggml.h via runtime/ggml_graph.cpp): one

@@ -180,6 +180,34 @@ int sample_from_candidates(const SampleOut & so, int k, float top_p, std::mt1993
     return sample_from_top_k(rng, cand, top_p);
 }
 
+// The reference's softmax(row)[target] (examples/perplexity/perplexity.cpp:6-20) per row of
+// logits [n][V], the same float operations in the same order with this host's expf: the maximum
+// from logits[0] on with std::max's rule, expf(x - max) as a float, the index-order double sum,
+// the float divided by it and rounded back.  A row with a target < 0 gets -1.0f.  The host twin of
+// launch_score_rows, and the path of a vocabulary the kernel does not take.
+void score_host(const float * logits, int n, int V, const int * targets, float * probs) {
+    for (int r = 0; r < n; ++r) {
+        const float * x = logits + (size_t) r * V;
+        if (targets[r] < 0) {
+            probs[r] = -1.0f;
+            continue;
+        }
+        float mx = x[0];
+        for (int i = 0; i < V; ++i) mx = (mx < x[i]) ? x[i] : mx;      // std::max(mx, x[i])
+        double sum = 0.0;
+        float et = 0.0f;
+        for (int i = 0; i < V; ++i) {
+            const float d = x[i] - mx;
+            const float e = expf(d);
+            sum += e;
+            if (i == targets[r]) et = e;
+        }
+        float p = et;
+        p /= sum;       // probs[i] /= sum_exp: a double division rounded to float
+        probs[r] = p;
+    }
+}
+
 }  // namespace lvk
 
 namespace {

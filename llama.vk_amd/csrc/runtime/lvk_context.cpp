@@ -129,6 +129,9 @@ void Context::init(const llama_context_params & p) {
         if (const char * e = getenv("LVK_SEQ_START")) seq = (unsigned) strtoul(e, nullptr, 0) & ((1u << 25) - 1);
     }
     logits_d = (float *) model.alloc(C * V * 4);
+    // the score kernel holds a row in registers; a larger vocabulary is scored on the host
+    // (test hook, tests/test_gpu_score.py: LVK_SCORE_HOST=1 sends any vocabulary that way)
+    score_on_host = V > (size_t) SCORE_MAX_VOCAB || (getenv("LVK_SCORE_HOST") && atoi(getenv("LVK_SCORE_HOST")) != 0);
     emb_d = (float *) model.alloc(E * 4);
     sp_d = (StepParams *) model.alloc(sizeof(StepParams));
     tok_d = (int *) model.alloc(C * 4);
@@ -514,6 +517,85 @@ void Context::eval_sample(int token, int n_past) {
     kv_n = n_past + 1;
 }
 
+// The scoring tail's buffers, n_ctx rows each: reserved into local owners, committed once nothing
+// can throw any more (the pattern of lvk_rows.cpp).
+void Context::score_reserve() {
+    if (sc_tgt_d) return;
+    const size_t C = (size_t) n_ctx;
+    const char * oom = "llama.vk_amd: out of memory for the scoring buffers";
+    DevPtr<int> td = dev_alloc<int>(C, oom), ad = dev_alloc<int>(C, oom);
+    DevPtr<float> pd = dev_alloc<float>(C, oom);
+    HostPtr<int> th = pinned_alloc<int>(C, oom), ah = pinned_alloc<int>(C, oom);
+    HostPtr<float> ph = pinned_alloc<float>(C, oom);
+    // commit
+    sc_tgt_d = std::move(td);
+    sc_amax_d = std::move(ad);
+    sc_prob_d = std::move(pd);
+    sc_tgt_h = std::move(th);
+    sc_amax_h = std::move(ah);
+    sc_prob_h = std::move(ph);
+}
+
+void Context::score_stage(const char * fn, int n, const int * targets, const float * probs) {
+    const int V = (int) model.hp.n_vocab;
+    const std::string f = std::string(fn) + ": ";
+    if (!targets || !probs) throw Error(f + "null argument");
+    if (n < 1 || n > n_ctx_user) throw Error(f + "the row count must be in 1..n_ctx");
+    for (int i = 0; i < n; ++i)
+        if (targets[i] >= V) throw Error(f + "target id out of range");
+    score_reserve();
+    std::memcpy(sc_tgt_h.get(), targets, sizeof(int) * (size_t) n);
+}
+
+void Context::enqueue_score(int n, bool want_argmax) {
+    const int V = (int) model.hp.n_vocab;
+    if (!score_on_host) {
+        LVK_HIP(hipMemcpyAsync(sc_tgt_d.get(), sc_tgt_h.get(), sizeof(int) * (size_t) n, hipMemcpyHostToDevice, stream));
+        LVK_HIP(launch_score_rows(logits_d, V, n, sc_tgt_d.get(), sc_prob_d.get(), stream));
+        LVK_HIP(hipMemcpyAsync(sc_prob_h.get(), sc_prob_d.get(), sizeof(float) * (size_t) n, hipMemcpyDeviceToHost, stream));
+    }
+    if (want_argmax) {
+        LVK_HIP(launch_argmax_rows(logits_d, V, n, sc_amax_d.get(), stream));
+        LVK_HIP(hipMemcpyAsync(sc_amax_h.get(), sc_amax_d.get(), sizeof(int) * (size_t) n, hipMemcpyDeviceToHost, stream));
+    }
+}
+
+void Context::score_collect(int n, float * probs, int * argmax) {
+    const size_t V = model.hp.n_vocab;
+    if (!score_on_host) {
+        std::memcpy(probs, sc_prob_h.get(), sizeof(float) * (size_t) n);
+    } else {
+        std::vector<float> row(V);
+        for (int i = 0; i < n; ++i) {
+            if (sc_tgt_h[i] >= 0) LVK_HIP(hipMemcpy(row.data(), logits_d + (size_t) i * V, V * sizeof(float), hipMemcpyDeviceToHost));
+            score_host(row.data(), 1, (int) V, &sc_tgt_h[i], &probs[i]);
+        }
+    }
+    if (argmax) std::memcpy(argmax, sc_amax_h.get(), sizeof(int) * (size_t) n);
+}
+
+// llama_eval(tokens, n, n_past) with the lm_head over every row (logits_all or not; one token: the
+// matvec lm_head, a batch: the prompt matmul), enqueued eagerly and ended by the score kernel:
+// probs[i] = softmax(row i)[targets[i]], -1.0f where targets[i] < 0.  The KV cache and its count
+// end as after eval(); the host logits are not refreshed.  Every argument is checked before
+// anything is enqueued.
+void Context::eval_score(const int * tokens, int n, int n_past, const int * targets, float * probs, int * argmax) {
+    const char * fn = "lvk_eval_score";
+    if (!model.has_head || !model.has_embed || link) throw Error(std::string(fn) + ": not available on a stage context");
+    if (!tokens) throw Error(std::string(fn) + ": null argument");
+    if (n < 1 || n_past < 0 || n > n_ctx_user || n_past > n_ctx_user - n) throw Error(std::string(fn) + ": n_past + n_tokens exceeds n_ctx");
+    for (int i = 0; i < n; ++i)
+        if (tokens[i] < 0 || tokens[i] >= (int) model.hp.n_vocab) throw Error(std::string(fn) + ": token id out of range");
+    score_stage(fn, n, targets, probs);
+    EvalPart part;
+    part.score = true;
+    part.score_argmax = argmax != nullptr;
+    drain_on_error(true, false, [&] { begin_eval(tokens, n, n_past, part); });
+    end_eval(true);     // llama_get_logits is stale from here on, as after eval_greedy
+    kv_n = n_past + n;
+    score_collect(n, probs, argmax);
+}
+
 void Context::fetch_logits() {
     const size_t V = model.hp.n_vocab;
     logits.resize(V);
@@ -542,13 +624,15 @@ void Context::begin_eval(const int * tokens, int n, int n_past, const EvalPart &
         throw Error("llama.vk_amd: n_past + n_tokens exceeds n_ctx");
     if ((part.greedy || part.sample) && (!model.has_head || n != 1 || logits_all))
         throw Error("llama.vk_amd: greedy / sampling eval needs the lm_head stage, one token and last-token logits");
+    if (part.score && (!model.has_head || !model.has_embed || part.n_total >= 0 || !sc_tgt_d))
+        throw Error("llama.vk_amd: a scoring eval needs the whole model in one slice and its targets staged");
     if (model.has_embed) {
         if (!tokens) throw Error("llama.vk_amd: the first stage needs tokens");
         for (int i = 0; i < n; ++i)
             if (tokens[i] < 0 || tokens[i] >= V) throw Error("llama.vk_amd: token id out of range");
         std::memcpy(tok_h.get() + part.tok_off, tokens, sizeof(int) * (size_t) n);
     }
-    const bool last_only = !logits_all;
+    const bool last_only = !logits_all && !part.score;      // a scoring eval: every row's logits, in HBM only
     const bool single = part.n_total < 0 || part.n_total == n;
     const bool graph_ok = n == 1 && last_only && single && use_graph && !profiling;
     // the graphs read step block 0; eager slices each take their own (the H2D copy reads
@@ -559,7 +643,7 @@ void Context::begin_eval(const int * tokens, int n, int n_past, const EvalPart &
     sh->n_tokens = n;
     sh->pad0 = (n == 1 && model.has_embed) ? tokens[0] : 0;
     sh->seq = next_seq();
-    if (model.has_head && part.tok_off == 0)   // within the reserve: the pointer never moves
+    if (model.has_head && part.tok_off == 0 && !part.score)   // within the reserve: the pointer never moves
         logits.resize((size_t) (last_only ? 1 : n_total) * V);
     if (graph_ok) {
         const DecodeGraph kind = part.greedy ? DecodeGraph::GREEDY : part.sample ? DecodeGraph::SAMPLE : DecodeGraph::LOGITS;
@@ -578,7 +662,9 @@ void Context::begin_eval(const int * tokens, int n, int n_past, const EvalPart &
         f.logit_row = last_only ? 0 : part.tok_off;
         f.head = part.head;
         enqueue_forward(f);
-        if (part.greedy) {
+        if (part.score) {
+            enqueue_score(n, part.score_argmax);
+        } else if (part.greedy) {
             enqueue_argmax();
         } else if (part.sample) {
             LVK_HIP(launch_sample_cand(logits_d, V, samp_d, sout_d, stream));
@@ -587,7 +673,7 @@ void Context::begin_eval(const int * tokens, int n, int n_past, const EvalPart &
                                    stream));
         }
     }
-    if (want_embedding && model.has_head && part.copy_out && !part.greedy && !part.sample) {
+    if (want_embedding && model.has_head && part.copy_out && !part.greedy && !part.sample && !part.score) {
         embedding.resize(hp.n_embd);
         LVK_HIP(hipMemcpyAsync(embedding.data(), emb_d, sizeof(float) * hp.n_embd, hipMemcpyDeviceToHost, stream));
     }

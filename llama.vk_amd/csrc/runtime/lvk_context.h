@@ -36,6 +36,9 @@ struct EvalPart {
     bool copy_out = true; // copy logits / embedding / the greedy token to the host after this slice
     bool greedy = false;  // end in the device argmax (lvk_eval_greedy) instead of the logits D2H
     bool sample = false;  // end in the device top-k candidates (lvk_eval_sample) instead of the logits D2H
+    bool score = false;   // lm_head over every row whatever logits_all says, ending in the score kernel over the
+                          //   targets staged in sc_tgt_h (lvk_eval_score) instead of the logits D2H
+    bool score_argmax = false;   // score: the rows' device argmax as well
 };
 
 struct Context {
@@ -175,6 +178,25 @@ struct Context {
                             int * out_tokens);
     // the checks of a batched decode step's rows; next[s]: the count slot s has after the step (-1: no row)
     std::vector<int> rows_check(const char * fn, const int * tokens, const int * seqs, const int * pos, int n);
+    // scoring (lvk_eval_score, lvk_decode_batch_score): the forward pass with the lm_head over every
+    // row, then launch_score_rows over logits_d; only probs (and the rows' argmax) cross PCIe.  The
+    // buffers hold n_ctx rows, device and page-locked, allocated by the first call (score_reserve).
+    DevPtr<int> sc_tgt_d, sc_amax_d;
+    DevPtr<float> sc_prob_d;
+    HostPtr<int> sc_tgt_h, sc_amax_h;
+    HostPtr<float> sc_prob_h;
+    bool score_on_host = false;      // n_vocab > SCORE_MAX_VOCAB (or env LVK_SCORE_HOST=1): score_host over the rows
+    void score_reserve();
+    // the targets' checks (messages under the caller's name), then the targets into sc_tgt_h
+    void score_stage(const char * fn, int n, const int * targets, const float * probs);
+    // after the forward pass: targets H2D, the score kernel, probs (and argmax) D2H into the pinned buffers
+    void enqueue_score(int n, bool want_argmax);
+    // after the stream sync: the pinned results to the caller (score_on_host: the scored rows one
+    // by one through score_host)
+    void score_collect(int n, float * probs, int * argmax);
+    void eval_score(const int * tokens, int n, int n_past, const int * targets, float * probs, int * argmax);
+    void decode_rows_score(const int * tokens, const int * seqs, const int * pos, int n, const int * targets, float * probs,
+                           int * argmax);
     // per sampled row of a step (sr_cap of them, grown on demand): the candidates (host-mapped)
     // and the kernel's record; sr_pool_cap ints of last-n windows back to back
     size_t sr_cap = 0, sr_pool_cap = 0;
@@ -286,6 +308,8 @@ int sample_logits(const float * pl, int n_logits, const int * last, int n_last, 
                   float repeat_penalty, std::mt19937 & rng);
 int sample_from_top_k(std::mt19937 & rng, std::vector<std::pair<float, int>> & cand, float top_p);
 int sample_from_candidates(const SampleOut & so, int k, float top_p, std::mt19937 & rng);
+// the reference's softmax(row)[target] per row of logits [n][V] on the host (llama_api.cpp; lvk_score_host)
+void score_host(const float * logits, int n, int V, const int * targets, float * probs);
 // exp mode of the softmax kernels (lvk_device.h exp_f16): 2, 1 or 0 after a device self-check
 int pick_exp_mode(const uint16_t * exp_tab_d);
 // fp16 exp / silu tables (ggml.c:2915-2927) built with this host's glibc expf

@@ -560,6 +560,73 @@ int lvk_decode_batch_sample(struct llama_context * ctx, const int * tokens, cons
     } catch (const lvk::Error & e) { return fail(__func__, e.msg); }
 }
 
+int lvk_decode_batch_score(struct llama_context * ctx, const int * tokens, const int * seqs, const int * pos, int n,
+                           const int * targets, float * probs, int * argmax) {
+    try {
+        if (!ctx) throw lvk::Error("null context");
+        if (ctx->split) throw lvk::Error("not available on a layer split");
+        lvk::Context & c = ctx->c;
+        const int64_t t0 = lvk::now_us();
+        c.decode_rows_score(tokens, seqs, pos, n, targets, probs, argmax);
+        c.t_eval_us += lvk::now_us() - t0;   // n decode evals (llama.cpp:1186-1195)
+        c.n_eval += n;
+        return 0;
+    } catch (const lvk::Error & e) { return fail(__func__, e.msg); }
+}
+
+int lvk_eval_score(struct llama_context * ctx, const int * tokens, int n_tokens, int n_past, const int * targets,
+                   float * probs, int * argmax) {
+    try {
+        if (!ctx) throw lvk::Error("null context");
+        if (ctx->split) throw lvk::Error("not available on a layer split");
+        lvk::Context & c = ctx->c;
+        const int64_t t0 = lvk::now_us();
+        c.eval_score(tokens, n_tokens, n_past, targets, probs, argmax);
+        const int64_t dt = lvk::now_us() - t0;
+        if (n_tokens == 1) { c.t_eval_us += dt; c.n_eval++; }          // as llama_eval counts it (llama.cpp:1186-1195)
+        else { c.t_p_eval_us += dt; c.n_p_eval += n_tokens; }
+        if (!c.has_evaluated_once) {
+            c.t_load_us = lvk::now_us() - c.t_start_us;
+            c.has_evaluated_once = true;
+        }
+        return 0;
+    } catch (const lvk::Error & e) { return fail(__func__, e.msg); }
+}
+
+static void score_args(const float * logits, int n, int V, const int * targets, const float * probs) {
+    if (!logits || !targets || !probs || n <= 0 || V <= 0 || (size_t) n * (size_t) V > ((size_t) 1 << 28))
+        throw lvk::Error("arguments out of range");
+    for (int i = 0; i < n; ++i)
+        if (targets[i] >= V) throw lvk::Error("target id out of range");
+}
+
+int lvk_score_host(const float * logits, int n, int V, const int * targets, float * probs) {
+    try {
+        score_args(logits, n, V, targets, probs);
+        lvk::score_host(logits, n, V, targets, probs);
+        return 0;
+    } catch (const lvk::Error & e) { return fail(__func__, e.msg); }
+}
+
+int lvk_score_rows(const float * logits, int n, int V, const int * targets, float * probs, int * argmax) {
+    try {
+        score_args(logits, n, V, targets, probs);
+        if (V > lvk::SCORE_MAX_VOCAB) throw lvk::Error("the kernel takes V <= 32768 (lvk_score_host takes any)");
+        lvk::Scratch dv;
+        float * xd = dv.up(logits, (size_t) n * V);
+        int * td = dv.up(targets, (size_t) n);
+        float * pd = (float *) dv.get((size_t) n * sizeof(float));
+        LVK_HIP(lvk::launch_score_rows(xd, V, n, td, pd, nullptr));
+        LVK_HIP(hipMemcpy(probs, pd, sizeof(float) * (size_t) n, hipMemcpyDeviceToHost));
+        if (argmax) {
+            int * ad = (int *) dv.get((size_t) n * sizeof(int));
+            LVK_HIP(lvk::launch_argmax_rows(xd, V, n, ad, nullptr));
+            LVK_HIP(hipMemcpy(argmax, ad, sizeof(int) * (size_t) n, hipMemcpyDeviceToHost));
+        }
+        return 0;
+    } catch (const lvk::Error & e) { return fail(__func__, e.msg); }
+}
+
 int lvk_seq_seed(struct llama_context * ctx, int seq, int seed) {
     if (!ctx || seq < 0 || seq >= ctx->c.seq_count()) return -1;
     if (seed <= 0) seed = (int) time(nullptr);      // as llama_init_from_file resolves it

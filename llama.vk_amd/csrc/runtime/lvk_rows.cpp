@@ -135,6 +135,23 @@ void Context::decode_rows(const int * tokens, const int * seqs, const int * pos,
     rows_finish(next);
 }
 
+// decode_rows' step ending in the score kernel (lvk_decode_batch_score): probs[i] =
+// softmax(row i)[targets[i]], -1.0f where targets[i] < 0; only probs (and the rows' argmax) cross
+// PCIe.  Every argument is checked before anything is enqueued.
+void Context::decode_rows_score(const int * tokens, const int * seqs, const int * pos, int n, const int * targets,
+                                float * probs, int * argmax_out) {
+    if (!slots_d) seq_init(1);
+    const std::vector<int> next = rows_check("lvk_decode_batch_score", tokens, seqs, pos, n);
+    score_stage("lvk_decode_batch_score", n, targets, probs);
+    drain_on_error(true, false, [&] {
+        rows_begin(tokens, seqs, pos, n, n == 1 ? tokens[0] : 0);
+        enqueue_forward(rows_forward(n));
+        enqueue_score(n, argmax_out != nullptr);
+    });
+    rows_finish(next);
+    score_collect(n, probs, argmax_out);
+}
+
 // room for `rows` sampled rows of a step and `pool` last-n ids: the host-mapped candidates, the
 // records and the pool, on the device and page-locked on the host; a buffer that is large enough stays
 void Context::rows_sample_reserve(size_t rows, size_t pool) {

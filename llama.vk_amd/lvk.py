@@ -149,6 +149,10 @@ _sig("lvk_seq_seed", C.c_int, [C.c_void_p, C.c_int, C.c_int])
 _sig("lvk_sample_fallbacks", C.c_int, [C.c_void_p])
 _sig("lvk_sample_candidates_rows", C.c_int, [f32p, C.c_int, C.c_int, i32p, C.c_int, i32p, f32p, f32p, i32p, i32p, f32p, i32p, i32p, i32p])
 _sig("lvk_rows_step", C.c_int, [f32p, C.c_int, C.c_int, i32p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
+_sig("lvk_score_rows", C.c_int, [f32p, C.c_int, C.c_int, i32p, C.c_void_p, C.c_void_p])
+_sig("lvk_score_host", C.c_int, [f32p, C.c_int, C.c_int, i32p, C.c_void_p])
+_sig("lvk_eval_score", C.c_int, [C.c_void_p, i32p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
+_sig("lvk_decode_batch_score", C.c_int, [C.c_void_p, i32p, i32p, i32p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
 _sig("lvk_init_stage", C.c_void_p, [C.c_char_p, llama_context_params, C.c_int, C.c_int])
 _sig("lvk_stage_eval", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int])
 _sig("lvk_stage_get_x", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int])
@@ -314,6 +318,38 @@ class Llama:
         if lib.lvk_decode_batch_sample(self.ctx, t, s, p, len(t), C.addressof(rows), out.ctypes.data) != 0:
             raise RuntimeError("lvk_decode_batch_sample failed")
         return out
+
+    # ---- scoring on the device (lvk_eval_score / lvk_decode_batch_score)
+    def eval_score(self, tokens, n_past, targets, argmax=False):
+        """llama_eval(tokens, n_past) with the lm_head over every row, ended by the score kernel
+        (lvk_eval_score): probs float32 [n], the reference's softmax(row i)[targets[i]], -1.0 where
+        targets[i] < 0; with argmax=True (probs, argmax int32 [n]).  Host logits are not refreshed."""
+        t = np.ascontiguousarray(tokens, np.int32).reshape(-1)
+        g = np.ascontiguousarray(targets, np.int32).reshape(-1)
+        if len(t) != len(g):
+            raise ValueError("eval_score: tokens and targets differ in length")
+        pr = np.empty(len(t), np.float32)
+        am = np.empty(len(t), np.int32) if argmax else None
+        if lib.lvk_eval_score(self.ctx, t, len(t), int(n_past), g.ctypes.data, pr.ctypes.data,
+                              am.ctypes.data if argmax else None) != 0:
+            raise RuntimeError("lvk_eval_score failed")
+        return (pr, am) if argmax else pr
+
+    def decode_batch_score(self, tokens, seqs, pos, targets, argmax=False):
+        """decode_batch's step over n rows ended by the score kernel (lvk_decode_batch_score): probs
+        float32 [n] as eval_score gives them; with argmax=True (probs, argmax int32 [n])."""
+        t = np.ascontiguousarray(tokens, np.int32).reshape(-1)
+        s = np.ascontiguousarray(seqs, np.int32).reshape(-1)
+        p = np.ascontiguousarray(pos, np.int32).reshape(-1)
+        g = np.ascontiguousarray(targets, np.int32).reshape(-1)
+        if not (len(t) == len(s) == len(p) == len(g)):
+            raise ValueError("decode_batch_score: tokens, seqs, pos and targets differ in length")
+        pr = np.empty(len(t), np.float32)
+        am = np.empty(len(t), np.int32) if argmax else None
+        if lib.lvk_decode_batch_score(self.ctx, t, s, p, len(t), g.ctypes.data, pr.ctypes.data,
+                                      am.ctypes.data if argmax else None) != 0:
+            raise RuntimeError("lvk_decode_batch_score failed")
+        return (pr, am) if argmax else pr
 
     def seq_seed(self, seq, seed):
         """reseed a slot's generator (slot 0: the context's, which sample / eval_sample draw from)"""
@@ -701,7 +737,64 @@ def rows_step(logits, forced, step):
     return am, dg, nt
 
 
-class _QuantizeFns(C.Structure):      # quantize_fns_t (include/ggml.h, reference ggml.h:808-813)
+def _score_args(logits, targets):
+    x = np.ascontiguousarray(logits, np.float32)
+    if x.ndim == 1:
+        x = x.reshape(1, -1)
+    g = np.ascontiguousarray(targets, np.int32).reshape(-1)
+    if x.ndim != 2 or len(g) != x.shape[0]:
+        raise ValueError("logits must be [n][V] with one target per row")
+    return x, g
+
+
+def score_rows(logits, targets, argmax=False):
+    """the device score kernel on host logits [n][V] (lvk_score_rows): probs float32 [n] =
+    softmax(row i)[targets[i]] by the reference's arithmetic, -1.0 where targets[i] < 0; with
+    argmax=True (probs, first-maximum argmax int32 [n])."""
+    x, g = _score_args(logits, targets)
+    pr = np.empty(len(g), np.float32)
+    am = np.empty(len(g), np.int32) if argmax else None
+    if lib.lvk_score_rows(x, x.shape[0], x.shape[1], g, pr.ctypes.data, am.ctypes.data if argmax else None) != 0:
+        raise RuntimeError("lvk_score_rows failed")
+    return (pr, am) if argmax else pr
+
+
+def score_host(logits, targets):
+    """the host twin of score_rows (lvk_score_host): the reference's softmax(row)[target]
+    (perplexity.cpp:6-20) with this host's expf, bit for bit"""
+    x, g = _score_args(logits, targets)
+    pr = np.empty(len(g), np.float32)
+    if lib.lvk_score_host(x, x.shape[0], x.shape[1], g, pr.ctypes.data) != 0:
+        raise RuntimeError("lvk_score_host failed")
+    return pr
+
+
+_logf = C.CDLL("libm.so.6").logf
+_logf.restype = C.c_float
+_logf.argtypes = [C.c_float]
+
+
+def perplexity(m, tokens, n_ctx):
+    """the loop of examples/perplexity (perplexity.cpp:28-77) on eval_score: chunk i holds the
+    n_ctx - 1 tokens from i * n_ctx on at n_past = 0, its rows j >= n_ctx / 2 are scored against
+    tokens[start + j + 1], nll += -logf(prob) in a double.  Returns the running perplexity after
+    each of the len(tokens) // n_ctx chunks, as the reference prints it."""
+    tokens = np.ascontiguousarray(tokens, np.int32).reshape(-1)
+    n_ctx = int(n_ctx)
+    nll, count, out = 0.0, 0, []
+    for i in range(len(tokens) // n_ctx):
+        start = i * n_ctx
+        targets = np.full(n_ctx - 1, -1, np.int32)
+        targets[n_ctx // 2:] = tokens[start + n_ctx // 2 + 1:start + n_ctx]
+        probs = m.eval_score(tokens[start:start + n_ctx - 1], 0, targets)
+        for p in probs[n_ctx // 2:]:
+            nll += -_logf(float(p))        # std::log(float): libm's logf, as the reference calls it
+        count += n_ctx - 1 - n_ctx // 2
+        out.append(float(np.exp(nll / count)))
+    return out
+
+
+class _QuantizeFns(C.Structure):     # quantize_fns_t (include/ggml.h, reference ggml.h:808-813)
     _fields_ = [("dequantize_row_q", C.c_void_p), ("quantize_row_q", C.c_void_p),
                 ("quantize_row_q_reference", C.c_void_p), ("vec_dot_q", C.c_void_p)]
 
