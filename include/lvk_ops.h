@@ -129,6 +129,57 @@ LVK_API int lvk_attention_rows(int type, const uint16_t * kc, const uint16_t * v
                                const float * q, const int * slots, const int * pos, int n, int n_embd, int n_head,
                                int n_ctx, float * out, void * blocks);
 
+/* The fused steps of a transformer layer as a context launches them (lvk_context.cpp
+ * enqueue_forward), each on host data: weights in file layout, f32 rows in, results out.
+ * type is the weight type (0 f32, 1 f16, 2 Q4_0, 3 Q4_1).  path selects the launcher:
+ *   0  what a context chooses for this n (n == 1: launch_matvec_auto; a batch: the generic kernels
+ *      for Q4 below 16 tokens, else the batched route)
+ *   1  launch_matvec_cu (n == 1: matvec_cu.hip / matvec_cu41.hip, or the one f16 / f32 matvec)
+ *   2  launch_matvec (the generic kernels of matvec_q4.hip / matvec_q41.hip, any n; f16 / f32: n == 1)
+ *   3  the batched route: launch_act (or launch_actq_to_image) + launch_mm
+ * Every argument is checked on the host before anything is uploaded (k % 256 == 0, 1 <= n <= 4096,
+ * path 1 with n > 1, null pointers, the limits named below): -1 with a message on stderr, nothing
+ * launched.  A (path, type, shape) a launcher has no kernel for returns -1 as well (its
+ * hipErrorNotSupported / hipErrorInvalidValue), with nothing written to the outputs.  The Q4 weight
+ * images are built as the model loader builds them, for path 3 including the prompt images
+ * (Q4_1 always, Q4_0 unless LVK_PROMPT_A16=0); the Q4 batched matmul needs 128 | rows.
+ *
+ * lvk_layer_qkv: q | k | v = W . quant(g * rms_norm(x[t])) for the n rows of x [n][k]; w is
+ * [3 * n_embd][k] (wq, wk, wv rows).  Row t is RoPE'd at n_past + t; q16_out [n][n_embd] receives
+ * the f16 queries, row n_past + t of kc ([n_ctx][n_embd] f16 bits) the keys and column n_past + t
+ * of vc ([n_embd][n_ctx]) the values.  kc / vc go up and come back whole.  fused = 1: EPI_QKV (paths
+ * 1, 2) or EPI_ROPE_KV (path 3, Q4 only); fused = 0: EPI_STORE, then launch_rope_kv.  n_embd is
+ * independent of k (the kernels read it in the epilogue only); n_embd % 32 == 0, head_dim % 4 == 0,
+ * n_ctx <= 16384, 0 <= n_past <= n_ctx - n.  f16 KV only.
+ *
+ * lvk_layer_resid: y[t] += W . conv(a[t]), w [m][k], a [n][k] f32, y [n][m] in / out.  input = 0:
+ * the kernel converts the f32 rows (PRO_ACTF: the W2 role of the CU kernels, f16, f32; launch_act
+ * on path 3); input = 1 (Q4 only): a is quantized by launch_quantize_act and handed over as
+ * PRO_ACTQ (the Wo role; launch_actq_to_image on path 3).  Every EPI_RESID kernel needs m % 8 == 0.
+ *
+ * lvk_layer_swiglu: u[t] = silu(W1 . a[t]) * (W3 . a[t]) with a = quant(g * rms_norm(x[t])), w1 / w3
+ * [f][k] each, interleaved per 4 rows as the loader fuses them.  Paths 1 and 3 give u_out [n][f]
+ * f32 (EPI_SWIGLU_F32), path 2 (Q4 only, f % 32 == 0) blocks_out, n rows of f / 32 blocks of
+ * quantize_row_q(u[t]) in the reference block layout (EPI_SWIGLU); the other output must be NULL.
+ *
+ * lvk_layer_ffn: the batch FFN pair, x[t] += W2 . conv(u[t]) with u as above; x [n][k] in / out,
+ * w2 [k][f], f % 256 == 0.  swiglu_q = 1 (Q4_0 only): EPI_SWIGLU_Q writes W2's operand image in the
+ * W1|W3 epilogue; swiglu_q = 0: EPI_SWIGLU_F32, launch_act, then EPI_RESID.
+ *
+ * lvk_embed_rows: x_out[i] = the dequantized / widened row tokens[i] of emb [n_vocab][n_embd] (file
+ * layout; launch_embed), every token in 0..n_vocab-1, n_embd % 32 == 0. */
+LVK_API int lvk_layer_qkv(int type, int path, const void * w, int n_embd, int n_head, int k, const float * g,
+                          const float * x, int n, int n_ctx, int n_past, int fused, uint16_t * kc, uint16_t * vc,
+                          uint16_t * q16_out);
+LVK_API int lvk_layer_resid(int type, int path, const void * w, int m, int k, const float * a, int n, int input,
+                            float * y);
+LVK_API int lvk_layer_swiglu(int type, int path, const void * w1, const void * w3, int f, int k, const float * g,
+                             const float * x, int n, float * u_out, void * blocks_out);
+LVK_API int lvk_layer_ffn(int type, const void * w1, const void * w3, const void * w2, int f, int k, const float * g,
+                          float * x, int n, int swiglu_q);
+LVK_API int lvk_embed_rows(int type, const void * emb, int n_vocab, int n_embd, const int * tokens, int n,
+                           float * x_out);
+
 /* Self-check of the softmax exp: the number of arguments h <= 0 (fp16 bits)
  * where the device's computed fp16(exp(h)) differs from this host's
  * table_exp_f16[h] (ggml.c:2915-2927) -- 0 when the device expf reproduces it,

@@ -415,6 +415,312 @@ int lvk_attention_rows(int type, const uint16_t * kc, const uint16_t * vc, int n
     } catch (const lvk::Error & e) { return fail(__func__, e.msg); }
 }
 
+}  // extern "C"
+
+// ---- the fused steps of a transformer layer (lvk_context.cpp enqueue_forward) on host data
+namespace {
+
+bool type_ok(int type) { return type == lvk::F32 || type == lvk::F16 || type == lvk::Q4_0 || type == lvk::Q4_1; }
+bool is_q4(int type) { return type == lvk::Q4_0 || type == lvk::Q4_1; }
+
+// bytes of a file-layout row of k weights
+size_t row_bytes(int type, int k) {
+    if (type == lvk::F32) return (size_t) k * 4;
+    if (type == lvk::F16) return (size_t) k * 2;
+    return (size_t) (k / 32) * block_bytes(type);
+}
+
+// the checks every layer entry point shares; nullptr when they pass
+const char * layer_args_bad(int type, int path, int k, int n) {
+    if (!type_ok(type)) return "type: 0 f32, 1 f16, 2 Q4_0, 3 Q4_1";
+    if (path < 0 || path > 3) return "path: 0 as a context chooses, 1 launch_matvec_cu, 2 launch_matvec, 3 launch_act + launch_mm";
+    if (k < 256 || k % 256) return "k must be a positive multiple of 256";
+    if (n < 1 || n > 4096) return "n must be in 1..4096";
+    if (path == 1 && n != 1) return "path 1 (launch_matvec_cu) takes n == 1";
+    return nullptr;
+}
+
+// path 0 of a batch: use_batched's rule (lvk_context.cpp): f16 / f32 weights from 2 tokens on,
+// the Q4 types from 16
+int batch_path(int type, int n) { return is_q4(type) && n < 16 ? 2 : 3; }
+
+// the device image of M rows (file layout: rows_a, then rows_b when the matrix is two stacked
+// ones), built as the model loader builds it (lvk_model.cpp repack): the octet image, and for the
+// batched route the prompt images of the Q4 types
+lvk::QMatrix layer_matrix(lvk::Scratch & dv, int type, const void * rows_a, int Ma, const void * rows_b, int Mb, int K,
+                          int interleave4, bool batched) {
+    const int M = Ma + Mb;
+    const size_t rb = row_bytes(type, K);
+    uint8_t * stage = (uint8_t *) dv.get((size_t) M * rb);
+    LVK_HIP(hipMemcpy(stage, rows_a, (size_t) Ma * rb, hipMemcpyHostToDevice));
+    if (Mb) LVK_HIP(hipMemcpy(stage + (size_t) Ma * rb, rows_b, (size_t) Mb * rb, hipMemcpyHostToDevice));
+    lvk::QMatrix q;
+    q.qtype = type; q.M = M; q.K = K;
+    if (type == lvk::F16) {
+        q.nib = (const uint4 *) dv.get(lvk::f16_image_bytes(M, K));
+        LVK_HIP(lvk::launch_repack_f16(stage, M, K, (uint4 *) q.nib, nullptr, interleave4));
+        return q;
+    }
+    if (type == lvk::F32) {
+        q.nib = (const uint4 *) dv.get(lvk::f32_image_bytes(M, K));
+        LVK_HIP(lvk::launch_repack_f32(stage, M, K, (uint4 *) q.nib, nullptr, interleave4));
+        return q;
+    }
+    q.nib = (const uint4 *) dv.get(lvk::qimage_nib_bytes(M, K));
+    q.scl = dv.get(lvk::qimage_scl_bytes(M, K, type));
+    LVK_HIP(lvk::launch_repack(stage, type, M, K, (uint4 *) q.nib, (void *) q.scl, nullptr, interleave4));
+    if (batched && type == lvk::Q4_1) {
+        q.a16 = dv.get(lvk::mm_a16_bytes(M, K));
+        q.side = dv.get(lvk::mm41_side_bytes(M, K));
+        LVK_HIP(lvk::launch_build_mm41(q, (void *) q.a16, (void *) q.side, nullptr));
+    } else if (batched && type == lvk::Q4_0 && lvk::prompt_a16_env()) {
+        q.a16 = dv.get(lvk::mm_a16_bytes(M, K));
+        LVK_HIP(lvk::launch_build_a16(q, (void *) q.a16, nullptr));
+    }
+    return q;
+}
+
+// an operand image for n rows of K (xm zeroed once, lvk_kernels.h ActImage)
+lvk::ActImage layer_image(lvk::Scratch & dv, int type, int n, int K) {
+    const lvk::ActImageBytes nbytes = lvk::act_image_bytes(type, n, K);
+    lvk::ActImage im;
+    im.xm = dv.get(nbytes.xm);
+    LVK_HIP(hipMemset(im.xm, 0, nbytes.xm));
+    if (nbytes.da) im.da = (float *) dv.get(nbytes.da);
+    if (nbytes.xs) im.xs = dv.get(nbytes.xs);
+    return im;
+}
+
+// x[n][K] (rms_norm * g when g) as the batched matmul's operand: enqueue_forward's `act`
+lvk::ActImage layer_act(int type, const float * xd, const float * gd, int n, int K, const lvk::ActImage & img) {
+    if (type == lvk::F32 && !gd) {
+        lvk::ActImage in;
+        in.xm = (void *) xd;
+        return in;
+    }
+    LVK_HIP(lvk::launch_act(type, xd, gd, n, K, img, nullptr));
+    return img;
+}
+
+hipError_t mv_by_path(int path, const lvk::MvLaunch & L, int pro, int epi) {
+    if (path == 1) return lvk::launch_matvec_cu(L, pro, epi, nullptr);
+    if (path == 2) return lvk::launch_matvec(L, pro, epi, nullptr);
+    return lvk::launch_matvec_auto(L, pro, epi, nullptr);
+}
+
+const uint16_t * silu_table(lvk::Scratch & dv) {
+    std::vector<uint16_t> te, ts;
+    lvk::host_fp16_tables(te, ts);
+    return dv.up(ts.data(), ts.size());
+}
+
+}  // namespace
+
+extern "C" {
+
+int lvk_layer_qkv(int type, int path, const void * w, int n_embd, int n_head, int k, const float * g, const float * x,
+                  int n, int n_ctx, int n_past, int fused, uint16_t * kc, uint16_t * vc, uint16_t * q16_out) {
+    try {
+        if (!w || !g || !x || !kc || !vc || !q16_out) return fail(__func__, "null argument");
+        if (const char * bad = layer_args_bad(type, path, k, n)) return fail(__func__, bad);
+        if (n_head < 1 || n_embd < 32 || n_embd % 32 || n_embd % n_head || (n_embd / n_head) % 4 || n_embd > 16384)
+            return fail(__func__, "need n_embd % 32 == 0, n_embd <= 16384 and a head_dim that is a multiple of 4");
+        if (n_ctx < 1 || n_ctx > 16384 || n_past < 0 || n_past > n_ctx - n)
+            return fail(__func__, "need 1 <= n_ctx <= 16384 and 0 <= n_past <= n_ctx - n");
+        if (fused != 0 && fused != 1) return fail(__func__, "fused: 0 or 1");
+        if (path == 0 && n > 1) path = batch_path(type, n);
+        if (path == 3 && fused && !lvk::mm_epi_supported(type, lvk::EPI_ROPE_KV))
+            return fail(__func__, "the batched matmul fuses RoPE + KV append for Q4_0 / Q4_1 only");
+        if (path == 3 && is_q4(type) && n_embd % 128) return fail(__func__, "the Q4 batched matmul needs n_embd % 128 == 0");
+        lvk::Scratch dv;
+        const int E = n_embd, hd = n_embd / n_head;
+        const size_t CE = (size_t) n_ctx * E;
+        const lvk::QMatrix q = layer_matrix(dv, type, w, 3 * E, nullptr, 0, k, 0, path == 3);
+        std::vector<float2> rt;
+        lvk::host_rope_table(rt, (size_t) n_ctx, (size_t) hd);
+        const float2 * rope = dv.up(rt.data(), rt.size());
+        lvk::StepParams sp{n_past, n, 0, 0};
+        const lvk::StepParams * spd = dv.up(&sp, 1);
+        const float * xd = dv.up(x, (size_t) n * k);
+        const float * gd = dv.up(g, (size_t) k);
+        uint16_t * kcd = dv.up(kc, CE);
+        uint16_t * vcd = dv.up(vc, CE);
+        uint16_t * q16 = (uint16_t *) dv.get((size_t) n * E * 2);
+        float * qkv32 = fused ? nullptr : (float *) dv.get((size_t) n * 3 * E * 4);
+        if (path == 3) {
+            const lvk::ActImage img = layer_image(dv, type, n, k);
+            lvk::MmLaunch L;
+            L.w = q; L.x = layer_act(type, xd, gd, n, k, img); L.N = n;
+            const lvk::RopeKV rk{rope, spd, n_ctx, E, hd, q16, kcd, vcd};
+            if (fused) {
+                L.rk = &rk;
+                LVK_HIP(lvk::launch_mm(L, lvk::EPI_ROPE_KV, nullptr));
+            } else {
+                L.y = qkv32; L.ldy = 3 * E;
+                LVK_HIP(lvk::launch_mm(L, lvk::EPI_STORE, nullptr));
+            }
+        } else {
+            lvk::MvLaunch a;
+            a.w = q; a.x = xd; a.g = gd; a.sp = spd; a.n_tokens = n;
+            a.q16 = q16; a.kc = kcd; a.vc = vcd; a.rope.cs = rope;
+            a.n_embd = E; a.head_dim = hd; a.n_ctx = n_ctx;
+            a.y = qkv32;
+            LVK_HIP(mv_by_path(path, a, lvk::PRO_NORM, fused ? lvk::EPI_QKV : lvk::EPI_STORE));
+        }
+        if (!fused) LVK_HIP(lvk::launch_rope_kv(qkv32, n, E, hd, rope, spd, n_ctx, q16, kcd, vcd, nullptr));
+        LVK_HIP(hipMemcpy(q16_out, q16, (size_t) n * E * 2, hipMemcpyDeviceToHost));
+        LVK_HIP(hipMemcpy(kc, kcd, CE * 2, hipMemcpyDeviceToHost));
+        LVK_HIP(hipMemcpy(vc, vcd, CE * 2, hipMemcpyDeviceToHost));
+        return 0;
+    } catch (const lvk::Error & e) { return fail(__func__, e.msg); }
+}
+
+int lvk_layer_resid(int type, int path, const void * w, int m, int k, const float * a, int n, int input, float * y) {
+    try {
+        if (!w || !a || !y) return fail(__func__, "null argument");
+        if (const char * bad = layer_args_bad(type, path, k, n)) return fail(__func__, bad);
+        if (m < 8 || m % 8 || m > (1 << 20)) return fail(__func__, "the EPI_RESID kernels need m % 8 == 0");
+        if (input != 0 && input != 1) return fail(__func__, "input: 0 f32 rows, 1 quantized blocks");
+        if (input == 1 && !is_q4(type)) return fail(__func__, "input 1 (quantized blocks) is for Q4_0 / Q4_1 weights");
+        if (path == 0 && n > 1) path = batch_path(type, n);
+        // a single token as a context runs it: the Q4 W2 role is the CU kernels' (PRO_ACTF)
+        if (path == 0 && input == 0 && is_q4(type)) path = 1;
+        if (path == 3 && is_q4(type) && m % 128) return fail(__func__, "the Q4 batched matmul needs m % 128 == 0");
+        lvk::Scratch dv;
+        const lvk::QMatrix q = layer_matrix(dv, type, w, m, nullptr, 0, k, 0, path == 3);
+        const float * ad = dv.up(a, (size_t) n * k);
+        float * yd = dv.up(y, (size_t) n * m);
+        lvk::ActQ aq;
+        if (input == 1) {
+            aq = actq_alloc(dv, (size_t) n, (size_t) k / 32);
+            LVK_HIP(lvk::launch_quantize_act(ad, n, k, type, aq, nullptr));
+        }
+        if (path == 3) {
+            const lvk::ActImage img = layer_image(dv, type, n, k);
+            lvk::MmLaunch L;
+            L.w = q; L.N = n; L.y = yd; L.ldy = m;
+            if (input == 1) {
+                LVK_HIP(lvk::launch_actq_to_image(type, aq, n, k, img, nullptr));
+                L.x = img;
+            } else {
+                L.x = layer_act(type, ad, nullptr, n, k, img);
+            }
+            LVK_HIP(lvk::launch_mm(L, lvk::EPI_RESID, nullptr));
+        } else {
+            lvk::StepParams sp{0, n, 0, 0};
+            lvk::MvLaunch b;
+            b.w = q; b.y = yd; b.sp = dv.up(&sp, 1); b.n_tokens = n;
+            if (input == 1) b.xq = aq; else b.x = ad;
+            LVK_HIP(mv_by_path(path, b, input == 1 ? lvk::PRO_ACTQ : lvk::PRO_ACTF, lvk::EPI_RESID));
+        }
+        LVK_HIP(hipMemcpy(y, yd, (size_t) n * m * 4, hipMemcpyDeviceToHost));
+        return 0;
+    } catch (const lvk::Error & e) { return fail(__func__, e.msg); }
+}
+
+int lvk_layer_swiglu(int type, int path, const void * w1, const void * w3, int f, int k, const float * g, const float * x,
+                     int n, float * u_out, void * blocks_out) {
+    try {
+        if (!w1 || !w3 || !g || !x) return fail(__func__, "null argument");
+        if (const char * bad = layer_args_bad(type, path, k, n)) return fail(__func__, bad);
+        if (f < 4 || f % 4 || f > (1 << 19)) return fail(__func__, "the interleaved W1|W3 image needs f % 4 == 0");
+        if (path == 0)
+            path = n > 1 ? batch_path(type, n)
+                         : lvk::matvec_cu_supported(k, type) && lvk::matvec_cu_supported(f, type) ? 1 : 2;
+        if (path == 2) {
+            if (!is_q4(type)) return fail(__func__, "path 2 (EPI_SWIGLU, quantized output) is for Q4_0 / Q4_1 weights");
+            if (!blocks_out || u_out) return fail(__func__, "path 2 produces blocks_out only");
+            if (f % 32) return fail(__func__, "path 2 needs f % 32 == 0");
+        } else {
+            if (!u_out || blocks_out) return fail(__func__, "paths 1 and 3 produce u_out only");
+            if (path == 3 && is_q4(type) && f % 64) return fail(__func__, "the Q4 batched matmul needs f % 64 == 0");
+        }
+        lvk::Scratch dv;
+        const lvk::QMatrix q = layer_matrix(dv, type, w1, f, w3, f, k, 1, path == 3);
+        const float * xd = dv.up(x, (size_t) n * k);
+        const float * gd = dv.up(g, (size_t) k);
+        const uint16_t * st = silu_table(dv);
+        if (path == 2) {
+            const lvk::ActQ out = actq_alloc(dv, (size_t) n, (size_t) f / 32);
+            lvk::StepParams sp{0, n, 0, 0};
+            lvk::MvLaunch c;
+            c.w = q; c.x = xd; c.g = gd; c.sp = dv.up(&sp, 1); c.n_tokens = n; c.silu_tab = st; c.out_q = out;
+            LVK_HIP(lvk::launch_matvec(c, lvk::PRO_NORM, lvk::EPI_SWIGLU, nullptr));
+            pack_blocks(type, out, (size_t) n * (f / 32), blocks_out);
+            return 0;
+        }
+        float * ud = (float *) dv.get((size_t) n * f * 4);
+        if (path == 3) {
+            const lvk::ActImage img = layer_image(dv, type, n, k);
+            lvk::MmLaunch L;
+            L.w = q; L.x = layer_act(type, xd, gd, n, k, img); L.N = n; L.y = ud; L.ldy = f; L.silu_tab = st;
+            LVK_HIP(lvk::launch_mm(L, lvk::EPI_SWIGLU_F32, nullptr));
+        } else {
+            lvk::StepParams sp{0, 1, 0, 0};
+            lvk::MvLaunch c;
+            c.w = q; c.x = xd; c.g = gd; c.sp = dv.up(&sp, 1); c.n_tokens = 1; c.silu_tab = st; c.u = ud;
+            LVK_HIP(lvk::launch_matvec_cu(c, lvk::PRO_NORM, lvk::EPI_SWIGLU_F32, nullptr));
+        }
+        LVK_HIP(hipMemcpy(u_out, ud, (size_t) n * f * 4, hipMemcpyDeviceToHost));
+        return 0;
+    } catch (const lvk::Error & e) { return fail(__func__, e.msg); }
+}
+
+int lvk_layer_ffn(int type, const void * w1, const void * w3, const void * w2, int f, int k, const float * g, float * x,
+                  int n, int swiglu_q) {
+    try {
+        if (!w1 || !w3 || !w2 || !g || !x) return fail(__func__, "null argument");
+        if (const char * bad = layer_args_bad(type, 3, k, n)) return fail(__func__, bad);
+        if (f < 256 || f % 256 || f > (1 << 19)) return fail(__func__, "f must be a positive multiple of 256");
+        if (swiglu_q != 0 && swiglu_q != 1) return fail(__func__, "swiglu_q: 0 or 1");
+        if (swiglu_q && !lvk::mm_epi_supported(type, lvk::EPI_SWIGLU_Q))
+            return fail(__func__, "swiglu_q = 1 (EPI_SWIGLU_Q) is for Q4_0 weights");
+        lvk::Scratch dv;
+        const lvk::QMatrix q13 = layer_matrix(dv, type, w1, f, w3, f, k, 1, true);
+        const lvk::QMatrix q2 = layer_matrix(dv, type, w2, k, nullptr, 0, f, 0, true);
+        float * xd = dv.up(x, (size_t) n * k);
+        const float * gd = dv.up(g, (size_t) k);
+        const uint16_t * st = silu_table(dv);
+        // one operand image for both matrices, as a context holds it (sized for the longer row)
+        const lvk::ActImage img = layer_image(dv, type, n, std::max(k, f));
+        lvk::MmLaunch a;
+        a.w = q13; a.x = layer_act(type, xd, gd, n, k, img); a.N = n; a.silu_tab = st;
+        lvk::MmLaunch b;
+        b.w = q2; b.N = n; b.y = xd; b.ldy = k; b.silu_tab = st;
+        if (swiglu_q) {
+            a.out = layer_image(dv, type, n, f);
+            LVK_HIP(lvk::launch_mm(a, lvk::EPI_SWIGLU_Q, nullptr));
+            b.x = a.out;
+        } else {
+            float * uf = (float *) dv.get((size_t) n * f * 4);
+            a.y = uf; a.ldy = f;
+            LVK_HIP(lvk::launch_mm(a, lvk::EPI_SWIGLU_F32, nullptr));
+            b.x = layer_act(type, uf, nullptr, n, f, img);
+        }
+        LVK_HIP(lvk::launch_mm(b, lvk::EPI_RESID, nullptr));
+        LVK_HIP(hipMemcpy(x, xd, (size_t) n * k * 4, hipMemcpyDeviceToHost));
+        return 0;
+    } catch (const lvk::Error & e) { return fail(__func__, e.msg); }
+}
+
+int lvk_embed_rows(int type, const void * emb, int n_vocab, int n_embd, const int * tokens, int n, float * x_out) {
+    try {
+        if (!emb || !tokens || !x_out) return fail(__func__, "null argument");
+        if (!type_ok(type)) return fail(__func__, "type: 0 f32, 1 f16, 2 Q4_0, 3 Q4_1");
+        if (n_vocab < 1 || n_vocab > (1 << 20) || n_embd < 32 || n_embd % 32 || n_embd > 16384 || n < 1 || n > 4096)
+            return fail(__func__, "need n_vocab >= 1, n_embd % 32 == 0 and 1 <= n <= 4096");
+        for (int i = 0; i < n; ++i)
+            if (tokens[i] < 0 || tokens[i] >= n_vocab) return fail(__func__, "a token id outside 0..n_vocab-1");
+        lvk::Scratch dv;
+        const uint8_t * ed = dv.up((const uint8_t *) emb, (size_t) n_vocab * row_bytes(type, n_embd));
+        const int * td = dv.up(tokens, (size_t) n);
+        float * xd = (float *) dv.get((size_t) n * n_embd * 4);
+        LVK_HIP(lvk::launch_embed(ed, type, n_embd, td, n, xd, nullptr));
+        LVK_HIP(hipMemcpy(x_out, xd, (size_t) n * n_embd * 4, hipMemcpyDeviceToHost));
+        return 0;
+    } catch (const lvk::Error & e) { return fail(__func__, e.msg); }
+}
+
 int lvk_exp_table_mismatches(void) {
     try {
         lvk::Scratch dv;

@@ -120,6 +120,14 @@ _sig("lvk_rope_kv_rows", C.c_int, [f32p, i32p, i32p, C.c_int, C.c_int, C.c_int, 
                                    u16p, u16p, u16p])
 _sig("lvk_attention_rows", C.c_int, [C.c_int, u16p, u16p, C.c_int, C.c_int, C.c_int, f32p, i32p, i32p, C.c_int, C.c_int,
                                      C.c_int, C.c_int, f32p, u8p])
+_sig("lvk_layer_qkv", C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
+_sig("lvk_layer_resid", C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p])
+_sig("lvk_layer_swiglu", C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                   C.c_int, C.c_void_p, C.c_void_p])
+_sig("lvk_layer_ffn", C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                C.c_int, C.c_int])
+_sig("lvk_embed_rows", C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p])
 _sig("lvk_rms_norm_mul", C.c_int, [f32p, f32p, C.c_int, C.c_int, f32p])
 _sig("lvk_exp_table_mismatches", C.c_int, [])
 _sig("lvk_attn_helpers_active", C.c_int, [C.c_int, C.c_int, C.c_int])
@@ -707,6 +715,99 @@ def attention_rows(qtype, kc, vc, layer, q, slots, pos, n_embd, n_head, n_ctx):
     _check(lib.lvk_attention_rows(qtype, kc.ravel(), vc.ravel(), n_slots, n_layer, layer, q, slots, pos, n, n_embd,
                                   n_head, n_ctx, out, blocks), "lvk_attention_rows")
     return out.reshape(n, n_embd), blocks.reshape(n, -1)
+
+
+WEIGHT_DTYPE = {0: np.float32, 1: np.uint16, 2: np.uint8, 3: np.uint8}
+
+
+def _weight_rows(wtype, w):
+    """file-layout rows of a matrix: f32 [m][k], f16 bits (uint16 or float16) [m][k], Q4 raw blocks uint8 [m][row
+    bytes]; returns (contiguous array or None, m)"""
+    if w is None:
+        return None, 0
+    w = np.ascontiguousarray(w)
+    if w.dtype == np.float16:
+        w = w.view(np.uint16)
+    w = np.ascontiguousarray(w, WEIGHT_DTYPE.get(wtype, np.uint8))
+    return w, w.shape[0]
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _f32(a):
+    return None if a is None else np.ascontiguousarray(a, np.float32)
+
+
+def layer_qkv(wtype, path, w, n_embd, n_head, k, g, x, n_ctx, n_past, kc, vc, fused=1, n=None):
+    """lvk_layer_qkv: w [3 * n_embd][k] rows in file layout, x [n][k], kc / vc [n_ctx * n_embd] uint16.
+    Returns (q16 [n][n_embd] uint16, kc, vc): the caches after the launch (the arguments are not changed)"""
+    w, _ = _weight_rows(wtype, w)
+    g, x = _f32(g), _f32(x)
+    if n is None:
+        n = x.reshape(-1, k).shape[0]
+    kc = None if kc is None else np.array(kc, np.uint16).ravel()
+    vc = None if vc is None else np.array(vc, np.uint16).ravel()
+    q16 = np.zeros(max(n, 1) * n_embd, np.uint16)
+    _check(lib.lvk_layer_qkv(wtype, path, _ptr(w), n_embd, n_head, k, _ptr(g), _ptr(x), n, n_ctx, n_past, fused,
+                             _ptr(kc), _ptr(vc), _ptr(q16)), "lvk_layer_qkv")
+    return q16.reshape(n, n_embd), kc, vc
+
+
+def layer_resid(wtype, path, w, k, a, y, input=0, n=None, m=None):
+    """lvk_layer_resid: w [m][k], a [n][k] f32, y [n][m] f32; returns y + W . conv(a) (y is not changed).
+    input 0: the kernel converts the f32 rows, 1 (Q4): a goes in as quantized blocks"""
+    w, rows = _weight_rows(wtype, w)
+    m = rows if m is None else m
+    a = _f32(a)
+    if n is None:
+        n = a.reshape(-1, k).shape[0]
+    y = None if y is None else np.array(y, np.float32)
+    _check(lib.lvk_layer_resid(wtype, path, _ptr(w), m, k, _ptr(a), n, input, _ptr(y)), "lvk_layer_resid")
+    return y.reshape(n, m)
+
+
+def layer_swiglu(wtype, path, w1, w3, k, g, x, want="u", n=None, f=None):
+    """lvk_layer_swiglu: w1 / w3 [f][k], x [n][k]; want "u": u [n][f] f32 (paths 1, 3), "blocks": the quantized
+    rows [n][f/32 * block bytes] uint8 (path 2, Q4), "both" / "none": what the library refuses"""
+    w1, rows = _weight_rows(wtype, w1)
+    w3, _ = _weight_rows(wtype, w3)
+    f = rows if f is None else f
+    g, x = _f32(g), _f32(x)
+    if n is None:
+        n = x.reshape(-1, k).shape[0]
+    u = np.zeros((max(n, 1), max(f, 1)), np.float32) if want in ("u", "both") else None
+    blocks = np.zeros((max(n, 1), max(f // 32, 1) * BLOCK_BYTES.get(wtype, 24)), np.uint8) if want in ("blocks", "both") else None
+    _check(lib.lvk_layer_swiglu(wtype, path, _ptr(w1), _ptr(w3), f, k, _ptr(g), _ptr(x), n, _ptr(u), _ptr(blocks)),
+           "lvk_layer_swiglu")
+    return u if want == "u" else blocks if want == "blocks" else (u, blocks)
+
+
+def layer_ffn(wtype, w1, w3, w2, k, g, x, swiglu_q=0, n=None, f=None):
+    """lvk_layer_ffn: the batch FFN pair; w1 / w3 [f][k], w2 [k][f], x [n][k]; returns x + W2 . conv(u) (x is not
+    changed).  swiglu_q 1 (Q4_0): the W1|W3 epilogue writes W2's operand image"""
+    w1, rows = _weight_rows(wtype, w1)
+    w3, _ = _weight_rows(wtype, w3)
+    w2, _ = _weight_rows(wtype, w2)
+    f = rows if f is None else f
+    g = _f32(g)
+    x = None if x is None else np.array(x, np.float32)
+    if n is None:
+        n = x.reshape(-1, k).shape[0]
+    _check(lib.lvk_layer_ffn(wtype, _ptr(w1), _ptr(w3), _ptr(w2), f, k, _ptr(g), _ptr(x), n, swiglu_q), "lvk_layer_ffn")
+    return x.reshape(n, k)
+
+
+def embed_rows(wtype, emb, n_embd, tokens, n_vocab=None):
+    """lvk_embed_rows: emb [n_vocab][n_embd] rows in file layout -> x [n][n_embd] f32 of the rows tokens[i]"""
+    emb, rows = _weight_rows(wtype, emb)
+    n_vocab = rows if n_vocab is None else n_vocab
+    tokens = None if tokens is None else np.ascontiguousarray(tokens, np.int32)
+    n = 0 if tokens is None else len(tokens)
+    x = np.zeros((max(n, 1), n_embd), np.float32)
+    _check(lib.lvk_embed_rows(wtype, _ptr(emb), n_vocab, n_embd, _ptr(tokens), n, _ptr(x)), "lvk_embed_rows")
+    return x[:n]
 
 
 def exp_table_mismatches():

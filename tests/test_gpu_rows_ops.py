@@ -20,6 +20,8 @@ import itertools
 import numpy as np
 import pytest
 
+from layer_ref import f16_bits
+
 pytestmark = pytest.mark.gpu
 
 E0, H0 = 512, 4
@@ -198,12 +200,6 @@ def test_rows_65b_heads(lvk, oracle):
 
 
 # ---- (f) RoPE + KV append
-
-def f16_bits(oracle, x):
-    """the oracle's GGML_FP32_TO_FP16 of every element"""
-    conv = oracle.lib.orc_fp32_to_fp16
-    return np.array([conv(float(v)) for v in np.asarray(x, np.float32).ravel()], np.uint16)
-
 
 ROWS_F = [(0, 0), (2, 255), (1, 17), (1, 18), (0, 128)]
 
