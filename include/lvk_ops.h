@@ -180,6 +180,29 @@ LVK_API int lvk_layer_ffn(int type, const void * w1, const void * w3, const void
 LVK_API int lvk_embed_rows(int type, const void * emb, int n_vocab, int n_embd, const int * tokens, int n,
                            float * x_out);
 
+/* The batched decode step's matmul (matvec_cols.hip, launch_matvec_cols) on host data: weights in
+ * file layout, f32 rows in, results out, with the bits of the lvk_layer_* entries above.  These are
+ * entries of their own: lvk_layer_* and its paths 0..3 stay as they are (path 0 keeps meaning the
+ * choice of a non-rows eval, and no path 4 or 5 exists).  Q4_0 (type 2) only, k 4096 or 11008
+ * (lvk_cols_resid) / 4096 (the other two), 2 <= n <= 4096, rows % 8 == 0.  Every argument is checked
+ * before anything is uploaded; an unsupported (type, k, n) returns -1 with a message and writes
+ * nothing.
+ *   lvk_cols_store   y[t] = W . quant(g * rms_norm(x[t])), w [m][k], x [n][k], y [n][m] out
+ *   lvk_cols_resid   y[t] += W . quant(a[t]), w [m][k], a [n][k] f32, y [n][m] in / out.  input 1: a is
+ *                    quantized by launch_quantize_act first (the Wo role), input 0: f32 rows (W2)
+ *   lvk_cols_swiglu  u[t] = silu(W1 . a[t]) * (W3 . a[t]), a = quant(g * rms_norm(x[t])), w1 / w3 [f][k]
+ *                    interleaved per 4 rows, f % 4 == 0, u_out [n][f] f32 */
+LVK_API int lvk_cols_store(int type, const void * w, int m, int k, const float * g, const float * x, int n, float * y);
+LVK_API int lvk_cols_resid(int type, const void * w, int m, int k, const float * a, int n, int input, float * y);
+LVK_API int lvk_cols_swiglu(int type, const void * w1, const void * w3, int f, int k, const float * g, const float * x,
+                            int n, float * u_out);
+
+/* 1 when a batched decode step (lvk_decode_batch and its chain / sample / score forms) of n rows
+ * on this context runs its matmuls through matvec_cols.hip, else 0: a Q4_0 model whose matrices have
+ * row lengths 4096 / 11008, 2 <= n <= the measured limit (lvk_context.cpp rows_cols_max), and not
+ * env LVK_ROWS_COLS=0 (read once per process). */
+LVK_API int lvk_rows_cols_active(struct llama_context * ctx, int n);
+
 /* Self-check of the softmax exp: the number of arguments h <= 0 (fp16 bits)
  * where the device's computed fp16(exp(h)) differs from this host's
  * table_exp_f16[h] (ggml.c:2915-2927) -- 0 when the device expf reproduces it,

@@ -123,6 +123,8 @@ struct MvLaunch {
     const uint16_t * silu_tab = nullptr;   // 64Ki fp16 table
     ActQ out_q;                            // quantized u = silu(w1 x) * (w3 x)
     float * u = nullptr;                   // EPI_SWIGLU_F32: u in f32 [N][M/2]
+    // launch_matvec_cols: scratch for the step's packed column image (matvec_cols_image_bytes)
+    void * cols_img = nullptr;
 };
 
 // dispatches on L.w.qtype: Q4_0 here (matvec_q4.hip), Q4_1, F16 and F32 forwarded.  Every matvec
@@ -150,6 +152,17 @@ inline hipError_t launch_matvec_auto(const MvLaunch & L, int pro, int epi, hipSt
 }
 // compute units of the current device (one decode workgroup per CU)
 int cu_count();
+
+// a batched decode step's matmul, n = L.n_tokens columns (matvec_cols.hip): one workgroup per CU
+// as launch_matvec_cu, the weights of a chunk applied to a tile of up to 16 columns held in LDS;
+// y / u are [n][M] / [n][M/2] as launch_matvec writes them, bit for bit.  Q4_0, K 4096 (EPI_STORE,
+// EPI_RESID, EPI_SWIGLU_F32) or 11008 (EPI_RESID), M % 8 == 0, n >= 2, tok0 == 0; the pairs
+// (PRO_NORM, EPI_STORE), (PRO_ACTQ, EPI_RESID), (PRO_ACTF, EPI_RESID), (PRO_NORM, EPI_SWIGLU_F32).
+// The step's rows are converted once into L.cols_img (matvec_cols_image_bytes(K, n) bytes) by a
+// launch of its own.  hipErrorNotSupported for anything else: the caller keeps its route.
+bool matvec_cols_supported(int qtype, int K, int n);
+size_t matvec_cols_image_bytes(int K, int n);
+hipError_t launch_matvec_cols(const MvLaunch & L, int pro, int epi, hipStream_t s);
 
 // token embedding rows: x[t] = dequant(tok_emb[tokens[t]]) (ggml.c:6868-6895)
 hipError_t launch_embed(const void * emb, int emb_type, int n_embd, const int * tokens, int n,

@@ -23,6 +23,13 @@
 
 namespace lvk {
 
+// the most rows of a batched decode step that take matvec_cols.hip (Context::rows_cols): the largest
+// measured S at which the route beat the one below it by more than twice the legs' run-to-run
+// spread (profiles/rows_cols_speed.json: 7B Q4_0, step ms new / old at S = 2, 4, 8, 16, 17, 24:
+// 2.30 / 3.14, 2.86 / 3.66, 3.57 / 5.75, 5.44 / 7.92, 6.87 / 8.23, 8.18 / 8.51; at 32, 48 and 64 the
+// MFMA matmuls win, 9.41 / 8.85, 13.38 / 10.68 and 17.35 / 11.52; 25..31 were not measured)
+constexpr int rows_cols_max = 24;
+
 int64_t now_us() {
     return std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now().time_since_epoch())
         .count();
@@ -119,6 +126,7 @@ void Context::init(const llama_context_params & p) {
         if (model.qtype == F16 || model.qtype == F32) attn_f32 = (float *) model.alloc(C * E * 4);
         qkv32 = (float *) model.alloc(C * 3 * E * 4);
         uf = (float *) model.alloc(C * F * 4);
+        if (model.qtype == Q4_0) cols_img = model.alloc(matvec_cols_image_bytes((int) std::max(E, F), rows_cols_max));
         prompt_exact = getenv("LVK_PROMPT_EXACT") && atoi(getenv("LVK_PROMPT_EXACT")) != 0;
         old_attention = getenv("LVK_ATTN_V1") && atoi(getenv("LVK_ATTN_V1")) != 0;
         attn_gran = model.alloc(attention_decode_scratch_bytes((int) H, (int) C));
@@ -221,6 +229,20 @@ static double qbytes(const QMatrix & w) {
     return (double) w.M * (w.K / 32) * (w.qtype == Q4_0 ? 20 : 24);
 }
 
+// A batched decode step of 2..rows_cols_max rows runs its matmuls on matvec_cols.hip: a Q4_0 model
+// whose four layer matrices and lm_head that file has row lengths for.  LVK_ROWS_COLS=0 (read once
+// per process) keeps the step on the routes below, for A/B runs.
+bool Context::rows_cols(int n) const {
+    static const bool on = [] { const char * e = getenv("LVK_ROWS_COLS"); return !e || atoi(e) != 0; }();
+    const int E = (int) model.hp.n_embd, F = (int) model.hp.n_ff();
+    if (!on || !cols_img || n < 2 || n > rows_cols_max || !model.has_head || !model.has_embed) return false;
+    if (!matvec_cols_supported(model.qtype, E, n) || !matvec_cols_supported(model.qtype, F, n)) return false;
+    auto fits = [&](const QMatrix & w, int K) { return w.qtype == Q4_0 && w.K == K && w.M % 8 == 0; };
+    for (const Layer & ly : model.layers)
+        if (!fits(ly.wqkv, E) || !fits(ly.wo, E) || !fits(ly.w13, E) || !fits(ly.w2, F)) return false;
+    return fits(model.output, E);
+}
+
 // batches go through the batched matmuls (launch_act + launch_mm) when every matrix of the
 // model fits them: f16 and f32 weights from 2 tokens on (their matvec is single-token only), the Q4
 // types from 16 (the MFMA tile is 16 tokens wide; below that the per-row VALU kernels win)
@@ -254,7 +276,8 @@ void Context::enqueue_forward(const Forward & f) {
     float * const logits_out = logits_d + (size_t) f.logit_row * hp.n_vocab;
     const int E = (int) hp.n_embd, H = (int) hp.n_head, hd = E / H, F = (int) hp.n_ff(), V = (int) hp.n_vocab;
     const int qt = model.qtype;
-    const bool batched = use_batched(n);
+    const bool cols = rows && rows_cols(n);
+    const bool batched = !cols && use_batched(n);
     const bool prompt_attn = !rows && n > 1 && !kv32 && attention_prompt_supported(E, H, n_ctx);
     const bool decode_attn = !rows && n == 1 && !old_attention && !kv32 && attention_decode_supported(E, H, n_ctx);
     if (decode_attn && !seq_epochs)
@@ -304,6 +327,22 @@ void Context::enqueue_forward(const Forward & f) {
             });
             timed_launch(K_ATTN, 0, [&] { return launch_attention_rows(at, rows_d.get(), slots_d.get(), layer_off, stream); });
         };
+        if (cols) {
+            // a batched decode step on matvec_cols.hip: every matrix streamed once per 16 rows
+            auto mvc = [&](int cls, const QMatrix & w, int pro, int epi, const float * xin, const float * g, float * y) {
+                MvLaunch m;
+                m.w = w; m.x = xin; m.g = g; m.n_tokens = n; m.cols_img = cols_img; m.silu_tab = silu_tab;
+                if (pro == PRO_ACTQ) m.xq = aq_attn;
+                if (epi == EPI_SWIGLU_F32) m.u = y; else m.y = y;
+                timed_launch(cls, qbytes(w), [&] { return launch_matvec_cols(m, pro, epi, stream); });
+            };
+            mvc(K_QKV, ly.wqkv, PRO_NORM, EPI_STORE, x, ly.attn_norm, qkv32);
+            rows_rope_attn();
+            mvc(K_WO, ly.wo, PRO_ACTQ, EPI_RESID, nullptr, nullptr, x);
+            mvc(K_W13, ly.w13, PRO_NORM, EPI_SWIGLU_F32, x, ly.ffn_norm, uf);
+            mvc(K_W2, ly.w2, PRO_ACTF, EPI_RESID, uf, nullptr, x);
+            continue;
+        }
         if (batched) {
             ActImage in = act(K_QKV, x, ly.attn_norm, E);
             if (rows) {
@@ -376,7 +415,11 @@ void Context::enqueue_forward(const Forward & f) {
         }
     }
     if (!model.has_head || !head) return;   // not the last pipeline stage: x is the output
-    if (batched && !last_only && mm_supported(model.output)) {
+    if (cols) {
+        MvLaunch o;
+        o.w = model.output; o.x = x; o.g = model.norm; o.y = logits_out; o.n_tokens = n; o.cols_img = cols_img;
+        timed_launch(K_LMHEAD, qbytes(model.output), [&] { return launch_matvec_cols(o, PRO_NORM, EPI_STORE, stream); });
+    } else if (batched && !last_only && mm_supported(model.output)) {
         // logits_all: lm_head over every row
         const ActImage in = act(K_LMHEAD, x, model.norm, E);
         mm(K_LMHEAD, model.output, in, logits_out, V, EPI_STORE);

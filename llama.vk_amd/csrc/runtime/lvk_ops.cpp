@@ -703,6 +703,82 @@ int lvk_layer_ffn(int type, const void * w1, const void * w3, const void * w2, i
     } catch (const lvk::Error & e) { return fail(__func__, e.msg); }
 }
 
+// ---- the batched decode step's matmul (launch_matvec_cols) on host data
+
+static const char * cols_args_bad(int type, int rows, int k, int n) {
+    if (!type_ok(type)) return "type: 0 f32, 1 f16, 2 Q4_0, 3 Q4_1";
+    if (k < 256 || k % 256) return "k must be a positive multiple of 256";
+    if (n < 1 || n > 4096) return "n must be in 1..4096";
+    if (rows < 8 || rows % 8 || rows > (1 << 20)) return "the matrix needs a multiple of 8 rows";
+    if (!lvk::matvec_cols_supported(type, k, n)) return "matvec_cols.hip takes Q4_0, k 4096 or 11008, n >= 2";
+    return nullptr;
+}
+
+int lvk_cols_store(int type, const void * w, int m, int k, const float * g, const float * x, int n, float * y) {
+    try {
+        if (!w || !g || !x || !y) return fail(__func__, "null argument");
+        if (const char * bad = cols_args_bad(type, m, k, n)) return fail(__func__, bad);
+        if (k != 4096) return fail(__func__, "EPI_STORE is compiled in for k 4096");
+        lvk::Scratch dv;
+        lvk::MvLaunch a;
+        a.w = layer_matrix(dv, type, w, m, nullptr, 0, k, 0, false);
+        a.x = dv.up(x, (size_t) n * k);
+        a.g = dv.up(g, (size_t) k);
+        a.n_tokens = n;
+        a.y = (float *) dv.get((size_t) n * m * 4);
+        a.cols_img = dv.get(lvk::matvec_cols_image_bytes(k, n));
+        LVK_HIP(lvk::launch_matvec_cols(a, lvk::PRO_NORM, lvk::EPI_STORE, nullptr));
+        LVK_HIP(hipMemcpy(y, a.y, (size_t) n * m * 4, hipMemcpyDeviceToHost));
+        return 0;
+    } catch (const lvk::Error & e) { return fail(__func__, e.msg); }
+}
+
+int lvk_cols_resid(int type, const void * w, int m, int k, const float * a, int n, int input, float * y) {
+    try {
+        if (!w || !a || !y) return fail(__func__, "null argument");
+        if (const char * bad = cols_args_bad(type, m, k, n)) return fail(__func__, bad);
+        if (input != 0 && input != 1) return fail(__func__, "input: 0 f32 rows, 1 quantized blocks");
+        lvk::Scratch dv;
+        lvk::MvLaunch b;
+        b.w = layer_matrix(dv, type, w, m, nullptr, 0, k, 0, false);
+        const float * ad = dv.up(a, (size_t) n * k);
+        b.y = dv.up(y, (size_t) n * m);
+        b.n_tokens = n;
+        b.cols_img = dv.get(lvk::matvec_cols_image_bytes(k, n));
+        if (input == 1) {
+            b.xq = actq_alloc(dv, (size_t) n, (size_t) k / 32);
+            LVK_HIP(lvk::launch_quantize_act(ad, n, k, type, b.xq, nullptr));
+        } else {
+            b.x = ad;
+        }
+        LVK_HIP(lvk::launch_matvec_cols(b, input == 1 ? lvk::PRO_ACTQ : lvk::PRO_ACTF, lvk::EPI_RESID, nullptr));
+        LVK_HIP(hipMemcpy(y, b.y, (size_t) n * m * 4, hipMemcpyDeviceToHost));
+        return 0;
+    } catch (const lvk::Error & e) { return fail(__func__, e.msg); }
+}
+
+int lvk_cols_swiglu(int type, const void * w1, const void * w3, int f, int k, const float * g, const float * x, int n,
+                    float * u_out) {
+    try {
+        if (!w1 || !w3 || !g || !x || !u_out) return fail(__func__, "null argument");
+        if (f < 4 || f % 4 || f > (1 << 19)) return fail(__func__, "the interleaved W1|W3 image needs f % 4 == 0");
+        if (const char * bad = cols_args_bad(type, 2 * f, k, n)) return fail(__func__, bad);
+        if (k != 4096) return fail(__func__, "EPI_SWIGLU_F32 is compiled in for k 4096");
+        lvk::Scratch dv;
+        lvk::MvLaunch c;
+        c.w = layer_matrix(dv, type, w1, f, w3, f, k, 1, false);
+        c.x = dv.up(x, (size_t) n * k);
+        c.g = dv.up(g, (size_t) k);
+        c.n_tokens = n;
+        c.silu_tab = silu_table(dv);
+        c.u = (float *) dv.get((size_t) n * f * 4);
+        c.cols_img = dv.get(lvk::matvec_cols_image_bytes(k, n));
+        LVK_HIP(lvk::launch_matvec_cols(c, lvk::PRO_NORM, lvk::EPI_SWIGLU_F32, nullptr));
+        LVK_HIP(hipMemcpy(u_out, c.u, (size_t) n * f * 4, hipMemcpyDeviceToHost));
+        return 0;
+    } catch (const lvk::Error & e) { return fail(__func__, e.msg); }
+}
+
 int lvk_embed_rows(int type, const void * emb, int n_vocab, int n_embd, const int * tokens, int n, float * x_out) {
     try {
         if (!emb || !tokens || !x_out) return fail(__func__, "null argument");
@@ -817,6 +893,10 @@ int lvk_seq_count(struct llama_context * ctx) { return ctx ? ctx->c.seq_count() 
 int lvk_seq_tokens(struct llama_context * ctx, int seq) {
     if (!ctx || seq < 0 || seq >= ctx->c.seq_count()) return -1;
     return ctx->c.seq_n(seq);
+}
+
+int lvk_rows_cols_active(struct llama_context * ctx, int n) {
+    return ctx && !ctx->split && ctx->c.rows_cols(n) ? 1 : 0;
 }
 
 int lvk_seq_copy(struct llama_context * ctx, int dst, int src, int n_tokens) {

@@ -131,6 +131,11 @@ _sig("lvk_embed_rows", C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void
 _sig("lvk_rms_norm_mul", C.c_int, [f32p, f32p, C.c_int, C.c_int, f32p])
 _sig("lvk_exp_table_mismatches", C.c_int, [])
 _sig("lvk_attn_helpers_active", C.c_int, [C.c_int, C.c_int, C.c_int])
+_sig("lvk_cols_store", C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p])
+_sig("lvk_cols_resid", C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p])
+_sig("lvk_cols_swiglu", C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                  C.c_void_p])
+_sig("lvk_rows_cols_active", C.c_int, [C.c_void_p, C.c_int])
 _sig("lvk_host_tables", None, [u16p, u16p])
 _sig("lvk_set_profiling", None, [C.c_void_p, C.c_int])
 _sig("lvk_get_profile", C.c_int, [C.c_void_p, f64p, i64p, f64p, C.c_int])
@@ -277,6 +282,11 @@ class Llama:
         if r != 0:
             raise RuntimeError("lvk_decode_batch failed")
         return lg, am
+
+    def rows_cols_active(self, n):
+        """1 when a batched decode step of n rows on this context runs its matmuls through
+        matvec_cols.hip (lvk_rows_cols_active), else 0"""
+        return int(lib.lvk_rows_cols_active(self.ctx, int(n)))
 
     def decode_batch_chain(self, forced, seqs, pos, n_steps, digests=False, logits=False):
         """n_steps batched decode steps in one call, one row per sequence (lvk_decode_batch_chain):
@@ -782,6 +792,44 @@ def layer_swiglu(wtype, path, w1, w3, k, g, x, want="u", n=None, f=None):
     _check(lib.lvk_layer_swiglu(wtype, path, _ptr(w1), _ptr(w3), f, k, _ptr(g), _ptr(x), n, _ptr(u), _ptr(blocks)),
            "lvk_layer_swiglu")
     return u if want == "u" else blocks if want == "blocks" else (u, blocks)
+
+
+def cols_store(wtype, w, k, g, x, n=None, m=None):
+    """lvk_cols_store (matvec_cols.hip): w [m][k], x [n][k]; returns y [n][m] = W . quant(g * rms_norm(x))"""
+    w, rows = _weight_rows(wtype, w)
+    m = rows if m is None else m
+    g, x = _f32(g), _f32(x)
+    if n is None:
+        n = x.reshape(-1, k).shape[0]
+    y = np.zeros((max(n, 1), max(m, 1)), np.float32)
+    _check(lib.lvk_cols_store(wtype, _ptr(w), m, k, _ptr(g), _ptr(x), n, _ptr(y)), "lvk_cols_store")
+    return y
+
+
+def cols_resid(wtype, w, k, a, y, input=0, n=None, m=None):
+    """lvk_cols_resid (matvec_cols.hip): w [m][k], a [n][k] f32, y [n][m]; returns y + W . quant(a) (y is not
+    changed).  input 0: f32 rows (the W2 role), 1: quantized blocks (the Wo role)"""
+    w, rows = _weight_rows(wtype, w)
+    m = rows if m is None else m
+    a = _f32(a)
+    if n is None:
+        n = a.reshape(-1, k).shape[0]
+    y = None if y is None else np.array(y, np.float32)
+    _check(lib.lvk_cols_resid(wtype, _ptr(w), m, k, _ptr(a), n, input, _ptr(y)), "lvk_cols_resid")
+    return y.reshape(n, m)
+
+
+def cols_swiglu(wtype, w1, w3, k, g, x, n=None, f=None):
+    """lvk_cols_swiglu (matvec_cols.hip): w1 / w3 [f][k], x [n][k]; returns u [n][f] f32"""
+    w1, rows = _weight_rows(wtype, w1)
+    w3, _ = _weight_rows(wtype, w3)
+    f = rows if f is None else f
+    g, x = _f32(g), _f32(x)
+    if n is None:
+        n = x.reshape(-1, k).shape[0]
+    u = np.zeros((max(n, 1), max(f, 1)), np.float32)
+    _check(lib.lvk_cols_swiglu(wtype, _ptr(w1), _ptr(w3), f, k, _ptr(g), _ptr(x), n, _ptr(u)), "lvk_cols_swiglu")
+    return u
 
 
 def layer_ffn(wtype, w1, w3, w2, k, g, x, swiglu_q=0, n=None, f=None):
