@@ -49,6 +49,12 @@ LVK_API int lvk_mul_mat_q_norm(int type, const void * w, int m, int k, const flo
  * (ggml.c:1950-2026 / 2188-2258).  Needs m % 128 == 0, k % 256 == 0, n >= 1. */
 LVK_API int lvk_mul_mat_q_mfma(int type, const void * w, int m, int k, const float * g, const float * x, int n,
                                float * y);
+/* The same with the weight source stated: images != 0 the f16 A-fragment image (Q4_1: with its side
+ * image), 0 the octet image the decode kernels read (Q4_0: k_mm_q40_mfma's unpack variant; Q4_1:
+ * mm_mfma41_nib.hip).  lvk_mul_mat_q_mfma itself takes Q4_1 on its images always and Q4_0 by env
+ * LVK_PROMPT_A16. */
+LVK_API int lvk_mul_mat_q_mfma_src(int type, const void * w, int m, int k, const float * g, const float * x, int n,
+                                   float * y, int images);
 
 /* f16 weights (ggml type 1): y[t][r] = ggml_vec_dot_f16(k, w_r, f16(a[t])) with a = x, or
  * a = g * rms_norm(x) when g != NULL, exactly as ggml_compute_forward_mul_mat_f16_f32 (AVX2)
@@ -202,6 +208,14 @@ LVK_API int lvk_cols_swiglu(int type, const void * w1, const void * w3, int f, i
  * row lengths 4096 / 11008, 2 <= n <= the measured limit (lvk_context.cpp rows_cols_max), and not
  * env LVK_ROWS_COLS=0 (read once per process). */
 LVK_API int lvk_rows_cols_active(struct llama_context * ctx, int n);
+
+/* 1 when an n-token eval on this context (every stage of a split) runs its layer matmuls as operand
+ * image + batched matmul (launch_act + launch_mm), else 0 (the per-row kernels). */
+LVK_API int lvk_prompt_batched(struct llama_context * ctx, int n);
+/* The weights the operator entry points (lvk_layer_* at path 3, lvk_mul_mat_q_mfma for Q4_0) give a
+ * batched matmul of this type under the present environment: 1 the octet image (LVK_PROMPT_A16=0),
+ * 2 the f16 A-fragment image (Q4_1: + side image); 0 for a type without the choice (f16, f32). */
+LVK_API int lvk_prompt_weight_source(int type);
 
 /* Self-check of the softmax exp: the number of arguments h <= 0 (fp16 bits)
  * where the device's computed fp16(exp(h)) differs from this host's

@@ -68,7 +68,8 @@ struct QMatrix {
     // weight bytes, saves the nibble unpack in k_mm_q40_mfma; nullptr = unpack path
     const void * a16 = nullptr;
     // Q4_1 only: the prompt matmul's per-block side image (launch_build_mm41: weight
-    // sums + d / m per lane); with a16 it enables the Q4_1 MFMA path (mm_mfma41.hip)
+    // sums + d / m per lane); with a16 it selects the Q4_1 kernels of mm_mfma41.hip, with neither
+    // the batched matmul reads the octet image (mm_mfma41_nib.hip)
     const void * side = nullptr;
 };
 
@@ -256,7 +257,8 @@ inline const uint4 * q41_wsum(const QMatrix & w) {
 //   Q4_0 (mm_mfma.hip): the matrix cores produce the per-chain integer partials, the VALU
 //     runs the reference fp32 chains.  Weights: the octet image, or QMatrix::a16 when built.
 //   Q4_1 (mm_mfma41.hip): the matrix cores also produce the cross-term sums and the scale
-//     products.  Weights: QMatrix::a16 + QMatrix::side, both from launch_build_mm41.
+//     products.  Weights: QMatrix::a16 + QMatrix::side, both from launch_build_mm41, or -- a
+//     matrix that has neither -- the octet image itself (mm_mfma41_nib.hip).
 //   F16 (mm_f16.hip): the fp32 chains of matvec_f16.hip, tiled over tokens.
 //   F32 (mm_f32.hip): the f32 matrix cores run the reference's fp32 chains themselves.
 // The activations reach the kernels as an operand image of the weight type:
@@ -332,6 +334,7 @@ hipError_t actq_image_q40(const ActQ & q, int N, int K, const ActImage & out, hi
 hipError_t actq_image_q41(const ActQ & q, int N, int K, const ActImage & out, hipStream_t s);
 hipError_t mm_q40(const MmLaunch & L, int epi, hipStream_t s);
 hipError_t mm_q41(const MmLaunch & L, int epi, hipStream_t s);
+hipError_t mm_q41_nib(const MmLaunch & L, int epi, hipStream_t s);   // a Q4_1 matrix without a16 / side
 hipError_t mm_f16(const MmLaunch & L, int epi, hipStream_t s);
 hipError_t mm_f32(const MmLaunch & L, int epi, hipStream_t s);
 

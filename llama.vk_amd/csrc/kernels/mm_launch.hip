@@ -1,6 +1,6 @@
 // mm_launch.hip -- the batched (N > 1) matmul interface of lvk_kernels.h: the weight-type
 // dispatch of launch_act / launch_actq_to_image / launch_mm with the checks every type shares
-// (the kernels are in mm_mfma.hip Q4_0, mm_mfma41.hip Q4_1, mm_f16.hip F16, mm_f32.hip F32), and the unfused
+// (the kernels are in mm_mfma.hip Q4_0, mm_mfma41.hip and mm_mfma41_nib.hip Q4_1, mm_f16.hip F16, mm_f32.hip F32), and the unfused
 // RoPE + KV append of stored Q|K|V rows.
 #include "mm_common.h"
 
@@ -13,7 +13,8 @@ static bool image_complete(int qtype, const ActImage & im) {
 bool mm_supported(const QMatrix & w) {
     switch (w.qtype) {
         case Q4_0: return w.M % MM_TM == 0 && w.K % 256 == 0;
-        case Q4_1: return w.a16 && w.side && w.M % MM_TM == 0 && w.K % 256 == 0;
+        // both prompt images (mm_mfma41.hip) or neither (mm_mfma41_nib.hip: the octet image)
+        case Q4_1: return !w.a16 == !w.side && w.M % MM_TM == 0 && w.K % 256 == 0;
         case F16: case F32: return w.M >= 1 && w.K % 256 == 0;
     }
     return false;

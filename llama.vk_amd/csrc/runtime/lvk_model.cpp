@@ -298,9 +298,9 @@ void load_model(Model & m, const std::string & path, bool vocab_only, hipStream_
     // prompt matmul's f16 A-fragment images (mm_mfma.hip, 2 B per weight: 13.2 GB for
     // 7B, 130 GB for 65B), decided by capacity (the A-image table):
     //   * Q4_1: the f16 image plus the per-block side image (mm_mfma41.hip, 3 B per weight in
-    //     all) are what the Q4_1 MFMA prompt path runs on -- 13B 512-token prompt 158 ms with
-    //     them, 1234 ms on the VALU kernels without -- built whenever they fit next to the Q4
-    //     images with 8 GiB to spare;
+    //     all) are what the faster Q4_1 MFMA kernels run on; without them the prompt stays on the
+    //     matrix cores and reads the octet image (mm_mfma41_nib.hip; the measured ratio is in
+    //     DESIGN.md section 9) -- built whenever they fit next to the Q4 images with 8 GiB to spare;
     //   * Q4_0: the nibble image runs the same MFMA path only 8-12 % slower (7B 44.3 vs 39.6 ms,
     //     65B 403 vs 372 ms), so the image (3.2x the Q4 bytes) is built only when it takes at
     //     most a quarter of the device's memory: 7B / 13B-shaped models and every stage of a

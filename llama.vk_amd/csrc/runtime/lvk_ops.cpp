@@ -140,10 +140,12 @@ static void mm_batched(lvk::Scratch & dv, const lvk::QMatrix & q, const float * 
     LVK_HIP(lvk::launch_mm(L, lvk::EPI_STORE, nullptr));
 }
 
-int lvk_mul_mat_q_mfma(int type, const void * w, int m, int k, const float * g, const float * x, int n, float * y) {
+// images: 1 the f16 A image (Q4_1: + side), 0 the octet image, -1 lvk_mul_mat_q_mfma's rule
+static int mul_mat_mfma_impl(const char * fn, int type, const void * w, int m, int k, const float * g, const float * x,
+                             int n, float * y, int images) {
     try {
-        if (type != lvk::Q4_0 && type != lvk::Q4_1) return fail(__func__, "Q4_0 / Q4_1 only");
-        if (m % 128 || k % 256 || n < 1) return fail(__func__, "need m % 128 == 0, k % 256 == 0, n >= 1");
+        if (type != lvk::Q4_0 && type != lvk::Q4_1) return fail(fn, "Q4_0 / Q4_1 only");
+        if (m % 128 || k % 256 || n < 1) return fail(fn, "need m % 128 == 0, k % 256 == 0, n >= 1");
         lvk::Scratch dv;
         const size_t nb = (size_t) k / 32;
         void * wd = dv.up((const uint8_t *) w, (size_t) m * nb * (type == lvk::Q4_0 ? 20 : 24));
@@ -152,11 +154,12 @@ int lvk_mul_mat_q_mfma(int type, const void * w, int m, int k, const float * g, 
         q.nib = (const uint4 *) dv.get(lvk::qimage_nib_bytes(m, k));
         q.scl = dv.get(lvk::qimage_scl_bytes(m, k, type));
         LVK_HIP(lvk::launch_repack(wd, type, m, k, (uint4 *) q.nib, (void *) q.scl, nullptr));
-        if (type == lvk::Q4_1) {            // the Q4_1 path always runs on its f16 + side images
+        if (images < 0) images = type == lvk::Q4_1 || lvk::prompt_a16_env();   // Q4_1: always its f16 + side images
+        if (images && type == lvk::Q4_1) {
             q.a16 = dv.get(lvk::mm_a16_bytes(m, k));
             q.side = dv.get(lvk::mm41_side_bytes(m, k));
             LVK_HIP(lvk::launch_build_mm41(q, (void *) q.a16, (void *) q.side, nullptr));
-        } else if (lvk::prompt_a16_env()) {  // the f16 A-fragment variant, as the model loader builds it
+        } else if (images) {                 // the f16 A-fragment variant, as the model loader builds it
             q.a16 = dv.get(lvk::mm_a16_bytes(m, k));
             LVK_HIP(lvk::launch_build_a16(q, (void *) q.a16, nullptr));
         }
@@ -166,7 +169,15 @@ int lvk_mul_mat_q_mfma(int type, const void * w, int m, int k, const float * g, 
         mm_batched(dv, q, xd, gd, n, yd);
         LVK_HIP(hipMemcpy(y, yd, (size_t) n * m * 4, hipMemcpyDeviceToHost));
         return 0;
-    } catch (const lvk::Error & e) { return fail(__func__, e.msg); }
+    } catch (const lvk::Error & e) { return fail(fn, e.msg); }
+}
+
+int lvk_mul_mat_q_mfma(int type, const void * w, int m, int k, const float * g, const float * x, int n, float * y) {
+    return mul_mat_mfma_impl(__func__, type, w, m, k, g, x, n, y, -1);
+}
+int lvk_mul_mat_q_mfma_src(int type, const void * w, int m, int k, const float * g, const float * x, int n, float * y,
+                           int images) {
+    return mul_mat_mfma_impl(__func__, type, w, m, k, g, x, n, y, images != 0);
 }
 
 int lvk_mul_mat_f16(const uint16_t * w, int m, int k, const float * g, const float * x, int n, float * y, int kernel) {
@@ -469,7 +480,7 @@ lvk::QMatrix layer_matrix(lvk::Scratch & dv, int type, const void * rows_a, int 
     q.nib = (const uint4 *) dv.get(lvk::qimage_nib_bytes(M, K));
     q.scl = dv.get(lvk::qimage_scl_bytes(M, K, type));
     LVK_HIP(lvk::launch_repack(stage, type, M, K, (uint4 *) q.nib, (void *) q.scl, nullptr, interleave4));
-    if (batched && type == lvk::Q4_1) {
+    if (batched && type == lvk::Q4_1 && lvk::prompt_a16_env()) {
         q.a16 = dv.get(lvk::mm_a16_bytes(M, K));
         q.side = dv.get(lvk::mm41_side_bytes(M, K));
         LVK_HIP(lvk::launch_build_mm41(q, (void *) q.a16, (void *) q.side, nullptr));
@@ -897,6 +908,18 @@ int lvk_seq_tokens(struct llama_context * ctx, int seq) {
 
 int lvk_rows_cols_active(struct llama_context * ctx, int n) {
     return ctx && !ctx->split && ctx->c.rows_cols(n) ? 1 : 0;
+}
+
+int lvk_prompt_batched(struct llama_context * ctx, int n) {
+    if (!ctx) return 0;
+    for (lvk::Context * c : ctx->stages())
+        if (!c->use_batched(n)) return 0;
+    return 1;
+}
+
+int lvk_prompt_weight_source(int type) {
+    if (type != lvk::Q4_0 && type != lvk::Q4_1) return 0;
+    return lvk::prompt_a16_env() ? 2 : 1;
 }
 
 int lvk_seq_copy(struct llama_context * ctx, int dst, int src, int n_tokens) {

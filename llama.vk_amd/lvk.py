@@ -109,6 +109,7 @@ _sig("lvk_quantize_rows", C.c_int, [C.c_int, f32p, C.c_int, C.c_int, u8p])
 _sig("lvk_mul_mat_q", C.c_int, [C.c_int, u8p, C.c_int, C.c_int, f32p, C.c_int, f32p])
 _sig("lvk_mul_mat_q_norm", C.c_int, [C.c_int, u8p, C.c_int, C.c_int, f32p, f32p, C.c_int, f32p])
 _sig("lvk_mul_mat_q_mfma", C.c_int, [C.c_int, u8p, C.c_int, C.c_int, C.c_void_p, f32p, C.c_int, f32p])
+_sig("lvk_mul_mat_q_mfma_src", C.c_int, [C.c_int, u8p, C.c_int, C.c_int, C.c_void_p, f32p, C.c_int, f32p, C.c_int])
 _sig("lvk_mul_mat_f16", C.c_int, [u16p, C.c_int, C.c_int, C.c_void_p, f32p, C.c_int, f32p, C.c_int])
 _sig("lvk_mul_mat_f32", C.c_int, [f32p, C.c_int, C.c_int, C.c_void_p, f32p, C.c_int, f32p, C.c_int])
 _sig("lvk_attention", C.c_int, [u16p, u16p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p])
@@ -136,6 +137,8 @@ _sig("lvk_cols_resid", C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void
 _sig("lvk_cols_swiglu", C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                   C.c_void_p])
 _sig("lvk_rows_cols_active", C.c_int, [C.c_void_p, C.c_int])
+_sig("lvk_prompt_batched", C.c_int, [C.c_void_p, C.c_int])
+_sig("lvk_prompt_weight_source", C.c_int, [C.c_int])
 _sig("lvk_host_tables", None, [u16p, u16p])
 _sig("lvk_set_profiling", None, [C.c_void_p, C.c_int])
 _sig("lvk_get_profile", C.c_int, [C.c_void_p, f64p, i64p, f64p, C.c_int])
@@ -287,6 +290,10 @@ class Llama:
         """1 when a batched decode step of n rows on this context runs its matmuls through
         matvec_cols.hip (lvk_rows_cols_active), else 0"""
         return int(lib.lvk_rows_cols_active(self.ctx, int(n)))
+
+    def prompt_batched(self, n):
+        """1 when an n-token eval runs its matmuls as operand image + batched matmul (lvk_prompt_batched)"""
+        return int(lib.lvk_prompt_batched(self.ctx, int(n)))
 
     def decode_batch_chain(self, forced, seqs, pos, n_steps, digests=False, logits=False):
         """n_steps batched decode steps in one call, one row per sequence (lvk_decode_batch_chain):
@@ -583,8 +590,15 @@ def mul_mat_q_norm(qtype, w_rows, m, k, g, x):
     return y.reshape(n, m)
 
 
-def mul_mat_q_mfma(qtype, w_rows, m, k, x, g=None):
-    """the MFMA prompt matmul (lvk_mul_mat_q_mfma); g: optional RMSNorm weight"""
+def prompt_weight_source(qtype):
+    """what the operator entry points feed a batched matmul of this type under the present environment:
+    1 the octet image, 2 the f16 A image, 0 no choice (lvk_prompt_weight_source)"""
+    return int(lib.lvk_prompt_weight_source(int(qtype)))
+
+
+def mul_mat_q_mfma(qtype, w_rows, m, k, x, g=None, images=None):
+    """the MFMA prompt matmul (lvk_mul_mat_q_mfma); g: optional RMSNorm weight; images: True the f16 A
+    image (Q4_1: + side), False the octet image (lvk_mul_mat_q_mfma_src), None the library's rule"""
     x = np.ascontiguousarray(x, np.float32)
     n = x.shape[0]
     y = np.zeros(n * m, np.float32)
@@ -592,8 +606,11 @@ def mul_mat_q_mfma(qtype, w_rows, m, k, x, g=None):
     if g is not None:
         g = np.ascontiguousarray(g, np.float32)
         gp = g.ctypes.data_as(C.c_void_p)
-    _check(lib.lvk_mul_mat_q_mfma(qtype, np.ascontiguousarray(w_rows, np.uint8).ravel(), m, k, gp, x, n, y),
-           "lvk_mul_mat_q_mfma")
+    wb = np.ascontiguousarray(w_rows, np.uint8).ravel()
+    if images is None:
+        _check(lib.lvk_mul_mat_q_mfma(qtype, wb, m, k, gp, x, n, y), "lvk_mul_mat_q_mfma")
+    else:
+        _check(lib.lvk_mul_mat_q_mfma_src(qtype, wb, m, k, gp, x, n, y, int(bool(images))), "lvk_mul_mat_q_mfma_src")
     return y.reshape(n, m)
 
 
