@@ -203,10 +203,21 @@ LVK_API int lvk_cols_resid(int type, const void * w, int m, int k, const float *
 LVK_API int lvk_cols_swiglu(int type, const void * w1, const void * w3, int f, int k, const float * g, const float * x,
                             int n, float * u_out);
 
+/* The same for Q4_1 weights (matvec_cols41.hip, launch_matvec_cols41): the argument lists and checks
+ * of the three entries above without `type`.  k 4096 or 5120 for lvk_cols41_store, lvk_cols41_swiglu
+ * and lvk_cols41_resid with input 1; k 11008 or 13824 for lvk_cols41_resid with input 0;
+ * 2 <= n <= 4096, rows % 8 == 0.  The images are built as the model loader builds them (the
+ * weight-sum image included). */
+LVK_API int lvk_cols41_store(const void * w, int m, int k, const float * g, const float * x, int n, float * y);
+LVK_API int lvk_cols41_resid(const void * w, int m, int k, const float * a, int n, int input, float * y);
+LVK_API int lvk_cols41_swiglu(const void * w1, const void * w3, int f, int k, const float * g, const float * x, int n,
+                              float * u_out);
+
 /* 1 when a batched decode step (lvk_decode_batch and its chain / sample / score forms) of n rows
- * on this context runs its matmuls through matvec_cols.hip, else 0: a Q4_0 model whose matrices have
- * row lengths 4096 / 11008, 2 <= n <= the measured limit (lvk_context.cpp rows_cols_max), and not
- * env LVK_ROWS_COLS=0 (read once per process). */
+ * on this context runs its matmuls through matvec_cols.hip or matvec_cols41.hip, else 0: a Q4_0
+ * model whose matrices have row lengths 4096 / 11008, or a Q4_1 model with 4096 / 11008 or 5120 /
+ * 13824, 2 <= n <= the type's measured limit (lvk_context.cpp rows_cols_max, rows_cols41_max), and
+ * not env LVK_ROWS_COLS=0 (read once per process). */
 LVK_API int lvk_rows_cols_active(struct llama_context * ctx, int n);
 
 /* 1 when an n-token eval on this context (every stage of a split) runs its layer matmuls as operand

@@ -164,6 +164,14 @@ int cu_count();
 bool matvec_cols_supported(int qtype, int K, int n);
 size_t matvec_cols_image_bytes(int K, int n);
 hipError_t launch_matvec_cols(const MvLaunch & L, int pro, int epi, hipStream_t s);
+// the same for Q4_1 weights (matvec_cols41.hip): the tile is up to 16 columns of K 4096 / 5120, 12 of
+// 11008, 8 of 13824.  K 4096 / 5120 with (PRO_NORM, EPI_STORE), (PRO_NORM, EPI_SWIGLU_F32) and
+// (PRO_ACTQ, EPI_RESID); K 11008 / 13824 with (PRO_ACTF, EPI_RESID); M % 8 == 0, n >= 2, tok0 == 0.
+// L.cols_img: matvec_cols41_image_bytes(K, n) bytes.  hipErrorNotSupported for anything else, with
+// nothing written.
+bool matvec_cols41_supported(int K, int n);
+size_t matvec_cols41_image_bytes(int K, int n);
+hipError_t launch_matvec_cols41(const MvLaunch & L, int pro, int epi, hipStream_t s);
 
 // token embedding rows: x[t] = dequant(tok_emb[tokens[t]]) (ggml.c:6868-6895)
 hipError_t launch_embed(const void * emb, int emb_type, int n_embd, const int * tokens, int n,

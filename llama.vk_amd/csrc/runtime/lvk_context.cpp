@@ -29,6 +29,12 @@ namespace lvk {
 // 2.30 / 3.14, 2.86 / 3.66, 3.57 / 5.75, 5.44 / 7.92, 6.87 / 8.23, 8.18 / 8.51; at 32, 48 and 64 the
 // MFMA matmuls win, 9.41 / 8.85, 13.38 / 10.68 and 17.35 / 11.52; 25..31 were not measured)
 constexpr int rows_cols_max = 24;
+// the same for a Q4_1 model on matvec_cols41.hip, by the same rule (profiles/rows_cols41_speed.json:
+// 13B-shaped Q4_1, step ms new / old at S = 2, 4, 8, 12, 15, 16, 17: 4.75 / 8.04, 6.56 / 13.85,
+// 10.84 / 23.72, 17.52 / 34.30, 18.67 / 42.96, 18.64 / 21.06, 21.71 / 23.18; at 24 and 32 the MFMA
+// matmuls win, 27.64 / 23.61 and 34.91 / 24.14; 18..23 were not measured.  The unmeasured S below 16
+// lie between two measured winners a < S < b with new(b) < old(a): DESIGN.md)
+constexpr int rows_cols41_max = 17;
 
 int64_t now_us() {
     return std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now().time_since_epoch())
@@ -127,6 +133,8 @@ void Context::init(const llama_context_params & p) {
         qkv32 = (float *) model.alloc(C * 3 * E * 4);
         uf = (float *) model.alloc(C * F * 4);
         if (model.qtype == Q4_0) cols_img = model.alloc(matvec_cols_image_bytes((int) std::max(E, F), rows_cols_max));
+        if (model.qtype == Q4_1 && matvec_cols41_supported((int) E, 2) && matvec_cols41_supported((int) F, 2))
+            cols_img = model.alloc(matvec_cols41_image_bytes((int) std::max(E, F), rows_cols41_max));
         prompt_exact = getenv("LVK_PROMPT_EXACT") && atoi(getenv("LVK_PROMPT_EXACT")) != 0;
         old_attention = getenv("LVK_ATTN_V1") && atoi(getenv("LVK_ATTN_V1")) != 0;
         attn_gran = model.alloc(attention_decode_scratch_bytes((int) H, (int) C));
@@ -230,14 +238,19 @@ static double qbytes(const QMatrix & w) {
 }
 
 // A batched decode step of 2..rows_cols_max rows runs its matmuls on matvec_cols.hip: a Q4_0 model
-// whose four layer matrices and lm_head that file has row lengths for.  LVK_ROWS_COLS=0 (read once
-// per process) keeps the step on the routes below, for A/B runs.
+// whose four layer matrices and lm_head that file has row lengths for; a Q4_1 model likewise on
+// matvec_cols41.hip, up to rows_cols41_max rows.  LVK_ROWS_COLS=0 (read once per process) keeps the
+// step on the routes below, for A/B runs.
 bool Context::rows_cols(int n) const {
     static const bool on = [] { const char * e = getenv("LVK_ROWS_COLS"); return !e || atoi(e) != 0; }();
-    const int E = (int) model.hp.n_embd, F = (int) model.hp.n_ff();
-    if (!on || !cols_img || n < 2 || n > rows_cols_max || !model.has_head || !model.has_embed) return false;
-    if (!matvec_cols_supported(model.qtype, E, n) || !matvec_cols_supported(model.qtype, F, n)) return false;
-    auto fits = [&](const QMatrix & w, int K) { return w.qtype == Q4_0 && w.K == K && w.M % 8 == 0; };
+    const int E = (int) model.hp.n_embd, F = (int) model.hp.n_ff(), qt = model.qtype;
+    if (!on || !cols_img || n < 2 || !model.has_head || !model.has_embed) return false;
+    if (qt == Q4_1) {
+        if (n > rows_cols41_max ||!matvec_cols41_supported(E, n) || !matvec_cols41_supported(F, n) || E > 5120 || F < 11008) return false;
+    } else if (n > rows_cols_max || !matvec_cols_supported(qt, E, n) || !matvec_cols_supported(qt, F, n)) {
+        return false;
+    }
+    auto fits = [&](const QMatrix & w, int K) { return w.qtype == qt && w.K == K && w.M % 8 == 0; };
     for (const Layer & ly : model.layers)
         if (!fits(ly.wqkv, E) || !fits(ly.wo, E) || !fits(ly.w13, E) || !fits(ly.w2, F)) return false;
     return fits(model.output, E);
@@ -328,13 +341,16 @@ void Context::enqueue_forward(const Forward & f) {
             timed_launch(K_ATTN, 0, [&] { return launch_attention_rows(at, rows_d.get(), slots_d.get(), layer_off, stream); });
         };
         if (cols) {
-            // a batched decode step on matvec_cols.hip: every matrix streamed once per 16 rows
+            // a batched decode step on matvec_cols.hip / matvec_cols41.hip: every matrix streamed
+            // once per tile of rows
             auto mvc = [&](int cls, const QMatrix & w, int pro, int epi, const float * xin, const float * g, float * y) {
                 MvLaunch m;
                 m.w = w; m.x = xin; m.g = g; m.n_tokens = n; m.cols_img = cols_img; m.silu_tab = silu_tab;
                 if (pro == PRO_ACTQ) m.xq = aq_attn;
                 if (epi == EPI_SWIGLU_F32) m.u = y; else m.y = y;
-                timed_launch(cls, qbytes(w), [&] { return launch_matvec_cols(m, pro, epi, stream); });
+                timed_launch(cls, qbytes(w), [&] {
+                    return qt == Q4_1 ? launch_matvec_cols41(m, pro, epi, stream) : launch_matvec_cols(m, pro, epi, stream);
+                });
             };
             mvc(K_QKV, ly.wqkv, PRO_NORM, EPI_STORE, x, ly.attn_norm, qkv32);
             rows_rope_attn();
@@ -418,7 +434,10 @@ void Context::enqueue_forward(const Forward & f) {
     if (cols) {
         MvLaunch o;
         o.w = model.output; o.x = x; o.g = model.norm; o.y = logits_out; o.n_tokens = n; o.cols_img = cols_img;
-        timed_launch(K_LMHEAD, qbytes(model.output), [&] { return launch_matvec_cols(o, PRO_NORM, EPI_STORE, stream); });
+        timed_launch(K_LMHEAD, qbytes(model.output), [&] {
+            return qt == Q4_1 ? launch_matvec_cols41(o, PRO_NORM, EPI_STORE, stream)
+                              : launch_matvec_cols(o, PRO_NORM, EPI_STORE, stream);
+        });
     } else if (batched && !last_only && mm_supported(model.output)) {
         // logits_all: lm_head over every row
         const ActImage in = act(K_LMHEAD, x, model.norm, E);

@@ -790,6 +790,79 @@ int lvk_cols_swiglu(int type, const void * w1, const void * w3, int f, int k, co
     } catch (const lvk::Error & e) { return fail(__func__, e.msg); }
 }
 
+// ---- the same for Q4_1 weights (launch_matvec_cols41); ff: the row length is an n_ff (the W2 role)
+
+static const char * cols41_args_bad(int rows, int k, int n, bool ff) {
+    if (n < 2 || n > 4096) return "n must be in 2..4096";
+    if (rows < 8 || rows % 8 || rows > (1 << 20)) return "the matrix needs a multiple of 8 rows";
+    if (ff ? (k != 11008 && k != 13824) : (k != 4096 && k != 5120))
+        return "matvec_cols41.hip takes k 4096 or 5120 (store, swiglu, resid input 1), 11008 or 13824 (resid input 0)";
+    return nullptr;
+}
+
+int lvk_cols41_store(const void * w, int m, int k, const float * g, const float * x, int n, float * y) {
+    try {
+        if (!w || !g || !x || !y) return fail(__func__, "null argument");
+        if (const char * bad = cols41_args_bad(m, k, n, false)) return fail(__func__, bad);
+        lvk::Scratch dv;
+        lvk::MvLaunch a;
+        a.w = layer_matrix(dv, lvk::Q4_1, w, m, nullptr, 0, k, 0, false);
+        a.x = dv.up(x, (size_t) n * k);
+        a.g = dv.up(g, (size_t) k);
+        a.n_tokens = n;
+        a.y = (float *) dv.get((size_t) n * m * 4);
+        a.cols_img = dv.get(lvk::matvec_cols41_image_bytes(k, n));
+        LVK_HIP(lvk::launch_matvec_cols41(a, lvk::PRO_NORM, lvk::EPI_STORE, nullptr));
+        LVK_HIP(hipMemcpy(y, a.y, (size_t) n * m * 4, hipMemcpyDeviceToHost));
+        return 0;
+    } catch (const lvk::Error & e) { return fail(__func__, e.msg); }
+}
+
+int lvk_cols41_resid(const void * w, int m, int k, const float * a, int n, int input, float * y) {
+    try {
+        if (!w || !a || !y) return fail(__func__, "null argument");
+        if (input != 0 && input != 1) return fail(__func__, "input: 0 f32 rows, 1 quantized blocks");
+        if (const char * bad = cols41_args_bad(m, k, n, input == 0)) return fail(__func__, bad);
+        lvk::Scratch dv;
+        lvk::MvLaunch b;
+        b.w = layer_matrix(dv, lvk::Q4_1, w, m, nullptr, 0, k, 0, false);
+        const float * ad = dv.up(a, (size_t) n * k);
+        b.y = dv.up(y, (size_t) n * m);
+        b.n_tokens = n;
+        b.cols_img = dv.get(lvk::matvec_cols41_image_bytes(k, n));
+        if (input == 1) {
+            b.xq = actq_alloc(dv, (size_t) n, (size_t) k / 32);
+            LVK_HIP(lvk::launch_quantize_act(ad, n, k, lvk::Q4_1, b.xq, nullptr));
+        } else {
+            b.x = ad;
+        }
+        LVK_HIP(lvk::launch_matvec_cols41(b, input == 1 ? lvk::PRO_ACTQ : lvk::PRO_ACTF, lvk::EPI_RESID, nullptr));
+        LVK_HIP(hipMemcpy(y, b.y, (size_t) n * m * 4, hipMemcpyDeviceToHost));
+        return 0;
+    } catch (const lvk::Error & e) { return fail(__func__, e.msg); }
+}
+
+int lvk_cols41_swiglu(const void * w1, const void * w3, int f, int k, const float * g, const float * x, int n,
+                      float * u_out) {
+    try {
+        if (!w1 || !w3 || !g || !x || !u_out) return fail(__func__, "null argument");
+        if (f < 4 || f % 4 || f > (1 << 19)) return fail(__func__, "the interleaved W1|W3 image needs f % 4 == 0");
+        if (const char * bad = cols41_args_bad(2 * f, k, n, false)) return fail(__func__, bad);
+        lvk::Scratch dv;
+        lvk::MvLaunch c;
+        c.w = layer_matrix(dv, lvk::Q4_1, w1, f, w3, f, k, 1, false);
+        c.x = dv.up(x, (size_t) n * k);
+        c.g = dv.up(g, (size_t) k);
+        c.n_tokens = n;
+        c.silu_tab = silu_table(dv);
+        c.u = (float *) dv.get((size_t) n * f * 4);
+        c.cols_img = dv.get(lvk::matvec_cols41_image_bytes(k, n));
+        LVK_HIP(lvk::launch_matvec_cols41(c, lvk::PRO_NORM, lvk::EPI_SWIGLU_F32, nullptr));
+        LVK_HIP(hipMemcpy(u_out, c.u, (size_t) n * f * 4, hipMemcpyDeviceToHost));
+        return 0;
+    } catch (const lvk::Error & e) { return fail(__func__, e.msg); }
+}
+
 int lvk_embed_rows(int type, const void * emb, int n_vocab, int n_embd, const int * tokens, int n, float * x_out) {
     try {
         if (!emb || !tokens || !x_out) return fail(__func__, "null argument");

@@ -136,6 +136,9 @@ _sig("lvk_cols_store", C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void
 _sig("lvk_cols_resid", C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p])
 _sig("lvk_cols_swiglu", C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                   C.c_void_p])
+_sig("lvk_cols41_store", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p])
+_sig("lvk_cols41_resid", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p])
+_sig("lvk_cols41_swiglu", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p])
 _sig("lvk_rows_cols_active", C.c_int, [C.c_void_p, C.c_int])
 _sig("lvk_prompt_batched", C.c_int, [C.c_void_p, C.c_int])
 _sig("lvk_prompt_weight_source", C.c_int, [C.c_int])
@@ -288,7 +291,7 @@ class Llama:
 
     def rows_cols_active(self, n):
         """1 when a batched decode step of n rows on this context runs its matmuls through
-        matvec_cols.hip (lvk_rows_cols_active), else 0"""
+        matvec_cols.hip (Q4_0) or matvec_cols41.hip (Q4_1) (lvk_rows_cols_active), else 0"""
         return int(lib.lvk_rows_cols_active(self.ctx, int(n)))
 
     def prompt_batched(self, n):
@@ -846,6 +849,44 @@ def cols_swiglu(wtype, w1, w3, k, g, x, n=None, f=None):
         n = x.reshape(-1, k).shape[0]
     u = np.zeros((max(n, 1), max(f, 1)), np.float32)
     _check(lib.lvk_cols_swiglu(wtype, _ptr(w1), _ptr(w3), f, k, _ptr(g), _ptr(x), n, _ptr(u)), "lvk_cols_swiglu")
+    return u
+
+
+def cols41_store(w, k, g, x, n=None, m=None):
+    """lvk_cols41_store (matvec_cols41.hip): Q4_1 w [m][k], x [n][k]; returns y [n][m] = W . quant(g * rms_norm(x))"""
+    w, rows = _weight_rows(3, w)
+    m = rows if m is None else m
+    g, x = _f32(g), _f32(x)
+    if n is None:
+        n = x.reshape(-1, k).shape[0]
+    y = np.zeros((max(n, 1), max(m, 1)), np.float32)
+    _check(lib.lvk_cols41_store(_ptr(w), m, k, _ptr(g), _ptr(x), n, _ptr(y)), "lvk_cols41_store")
+    return y
+
+
+def cols41_resid(w, k, a, y, input=0, n=None, m=None):
+    """lvk_cols41_resid (matvec_cols41.hip): Q4_1 w [m][k], a [n][k] f32, y [n][m]; returns y + W . quant(a) (y is
+    not changed).  input 0: f32 rows (the W2 role), 1: quantized blocks (the Wo role)"""
+    w, rows = _weight_rows(3, w)
+    m = rows if m is None else m
+    a = _f32(a)
+    if n is None:
+        n = a.reshape(-1, k).shape[0]
+    y = None if y is None else np.array(y, np.float32)
+    _check(lib.lvk_cols41_resid(_ptr(w), m, k, _ptr(a), n, input, _ptr(y)), "lvk_cols41_resid")
+    return y.reshape(n, m)
+
+
+def cols41_swiglu(w1, w3, k, g, x, n=None, f=None):
+    """lvk_cols41_swiglu (matvec_cols41.hip): Q4_1 w1 / w3 [f][k], x [n][k]; returns u [n][f] f32"""
+    w1, rows = _weight_rows(3, w1)
+    w3, _ = _weight_rows(3, w3)
+    f = rows if f is None else f
+    g, x = _f32(g), _f32(x)
+    if n is None:
+        n = x.reshape(-1, k).shape[0]
+    u = np.zeros((max(n, 1), max(f, 1)), np.float32)
+    _check(lib.lvk_cols41_swiglu(_ptr(w1), _ptr(w3), f, k, _ptr(g), _ptr(x), n, _ptr(u)), "lvk_cols41_swiglu")
     return u
 
 

@@ -9,6 +9,9 @@ others), and is repeated at the same positions (a rewind).  Per S: the median st
 argmax; aggregate tok/s = S / step time.  The yardstick is llama_eval (the captured decode graph)
 on slot 0 at the 64 positions.  The per-class device profile is taken at S = 16.  Appends one
 record per model to the JSON file (default profiles/seq_batch_speed.json) and prints it.
+--sweep S,S,...: these step sizes instead; --profile-at S,S,...: the per-class profile at these;
+--argmax-only: skip the logits-to-host leg (the A/B legs of profiles/rows_cols41_speed.json: one
+process per leg and repeat, LVK_ROWS_COLS=0 for the old route).
 --chain [--repeats R] [--parent FILE ...]: the chained leg instead (run_chain): lvk_decode_batch_chain
 against the host-fed legs, every leg R times, into profiles/seq_chain_speed.json; FILEs are records
 this tool wrote at the parent commit.
@@ -50,13 +53,13 @@ def median_ms(fn, steps, warm=3):
     return float(np.median(ts)) * 1e3
 
 
-def run(name, steps):
+def run(name, steps, sweep=None, profile_at=(16,), argmax_only=False):
     fn, cfg = CFG[name]
     path = os.path.join('/tmp/lvk_bench', fn)
     if not os.path.exists(path):
         os.makedirs(os.path.dirname(path), exist_ok=True)
         lvk.gen_model(path, vocab=os.path.join(ROOT, 'tests', 'golden', 'vocab32000.bin'), **cfg)
-    sweep = [1, 2, 4, 8, 16, 32, 64] if name == '7b' else [16]
+    sweep = sweep or ([1, 2, 4, 8, 16, 32, 64] if name == '7b' else [16])
     m = lvk.Llama(path, n_ctx=N_CTX)
     toks = np.array([1] + [100 + (i * 7919) % 31000 for i in range(1, N_CTX - 1)], np.int32)
     m.eval(toks, 0)
@@ -82,12 +85,13 @@ def run(name, steps):
         for s, p in enumerate(pos):
             m.seq_copy(1 + s, 0, p)
         seqs = [1 + s for s in range(S)]
-        ms = median_ms(lambda: m.decode_batch(row_tok[:S], seqs, pos), steps)
         ms_am = median_ms(lambda: m.decode_batch(row_tok[:S], seqs, pos, logits=False, argmax=True), steps)
+        ms = ms_am if argmax_only else median_ms(lambda: m.decode_batch(row_tok[:S], seqs, pos), steps)
         line = {'S': S, 'step_ms': round(ms, 3), 'tok_s': round(S / ms * 1e3, 1),
                 'vs_single': round(S / ms * 1e3 / single['tok_s'], 2),
-                'argmax_only_step_ms': round(ms_am, 3), 'argmax_only_tok_s': round(S / ms_am * 1e3, 1)}
-        if S == 16:
+                'argmax_only_step_ms': round(ms_am, 3), 'argmax_only_tok_s': round(S / ms_am * 1e3, 1),
+                'rows_cols_active': m.rows_cols_active(S)}
+        if S in profile_at:
             m.set_profiling(True)
             m.reset_profile()
             for _ in range(4):
@@ -277,7 +281,7 @@ def run_sample(name, steps, repeats):
 
 def main():
     args = sys.argv[1:]
-    steps, out = 20, None
+    steps, out, sweep, profile_at, argmax_only = 20, None, None, (16,), False
     names, chain, repeats, parents, sample = [], False, 3, [], False
     while args:
         a = args.pop(0)
@@ -285,6 +289,12 @@ def main():
             steps = int(args.pop(0))
         elif a == '--out':
             out = args.pop(0)
+        elif a == '--sweep':
+            sweep = [int(v) for v in args.pop(0).split(',')]
+        elif a == '--profile-at':
+            profile_at = tuple(int(v) for v in args.pop(0).split(','))
+        elif a == '--argmax-only':
+            argmax_only = True
         elif a == '--chain':
             chain = True
         elif a == '--sample':
@@ -300,7 +310,8 @@ def main():
     recs = json.load(open(out)) if os.path.exists(out) else []
     for name in names or ['7b']:
         rec = (run_sample(name, steps, repeats) if sample else
-               run_chain(name, steps, repeats, parents) if chain else run(name, steps))
+               run_chain(name, steps, repeats, parents) if chain else
+               run(name, steps, sweep, profile_at, argmax_only))
         recs = [r for r in recs if r['model'] != rec['model']] + [rec]
         print(json.dumps(rec), flush=True)
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
