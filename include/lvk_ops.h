@@ -87,7 +87,8 @@ LVK_API int lvk_attention_scores(const uint16_t * kc, const uint16_t * vc, const
 
 /* lvk_attention through the prompt-batch kernels (attention_prompt.hip: scores +
  * softmax per 32 query tokens, P.V per 32-dim slice); same result bits.  Needs
- * head_dim 128, n_ctx % 32 == 0, n_ctx <= 1024. */
+ * head_dim 128, n_ctx % 32 == 0, n_ctx <= 1024 (the kernels' LDS holds n_ctx positions; a
+ * context past that runs lvk_attention_long's kernels). */
 LVK_API int lvk_attention_prompt(const uint16_t * kc, const uint16_t * vc, const float * q, int n_embd, int n_head,
                                  int n_ctx, int n_past, int n, float * out);
 
@@ -110,6 +111,20 @@ LVK_API int lvk_attn_helpers_active(int n_embd, int n_head, int n_ctx);
  * limits of their functions; every kind needs head_dim 128, n >= 1, 0 <= n_past <= n_ctx - n. */
 LVK_API int lvk_attention_q(int kind, int type, const uint16_t * kc, const uint16_t * vc, const float * q, int n_embd,
                             int n_head, int n_ctx, int n_past, int n, float * out, void * blocks);
+
+/* lvk_attention_q through the long-context prompt kernels (attention_prompt_long.hip: K tiles
+ * split over the waves with score rows as long as n_past + n, V and P streamed through LDS in
+ * position tiles); same result bits.  type 2 (Q4_0) or 3 (Q4_1), blocks optional.  Needs head_dim
+ * 128, n_ctx % 32 == 0, 32 <= n_ctx <= 2048, n >= 1, 0 <= n_past <= n_ctx - n; every argument is
+ * checked before anything is uploaded: -1 with a message on stderr, nothing launched. */
+LVK_API int lvk_attention_long(int type, const uint16_t * kc, const uint16_t * vc, const float * q, int n_embd,
+                               int n_head, int n_ctx, int n_past, int n, float * out, void * blocks);
+
+/* Which attention an n-token llama_eval on this context runs (the forward pass takes the same
+ * decision): 0 attention.hip, 1 attention_prompt.hip, 2 attention_prompt_long.hip (contexts of
+ * 1025..2048 positions; 0 instead with env LVK_ATTN_LONG=0 when the context was created), 3 the
+ * decode kernels (n == 1).  -1 for n < 1 or a null context. */
+LVK_API int lvk_prompt_attn_path(struct llama_context * ctx, int n);
 
 /* The two kernels of a batched decode layer (attention_rows.hip) on host data.  A cache argument
  * is a host array [n_slots][n_layer][n_ctx * n_embd] of f16 bits (K [n_ctx][n_embd], V

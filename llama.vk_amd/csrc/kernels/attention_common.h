@@ -1,10 +1,12 @@
 // attention_common.h -- the reference-defined arithmetic the attention kernels share
 // (attention.hip, attention_decode.hip, attention_prompt.hip; graph_ops.hip for the graph
 // evaluator's soft_max and mul_mat): the ggml_vec_dot_f16 reduce (ggml.c:1781-1815), the
-// workgroup reductions of a softmax row (ggml.c:7099-7121), and what the launchers agree on.
+// workgroup reductions of a softmax row (ggml.c:7099-7121), the Wo-input epilogue of the prompt
+// P.V kernels (attention_prompt.hip, attention_prompt_long.hip), and what the launchers agree on.
 // Device-only: include it from .hip files.
 #pragma once
 #include "lvk_device.h"
+#include "mm_common.h"
 
 #include <cmath>
 #include <type_traits>
@@ -91,6 +93,45 @@ __device__ __forceinline__ double wg_sum_d(double v, double * redd, Bar && bar) 
     if ((threadIdx.x & 63) == 0) redd[threadIdx.x >> 6] = v;
     bar();
     return (redd[0] + redd[1]) + (redd[2] + redd[3]);
+}
+
+// The epilogue of a prompt P.V workgroup (256 threads): ob [32 tokens][33] holds the f32 results
+// of the 32-dim slice d0..d0+31 (one Q4 block of the merged heads) of tokens t0..t0+nt-1.  Written
+// as the f32 rows (out_f32 given), and quantized (quantize_row_q4_0, ggml.c:621-685, or
+// quantize_row_q4_1, ggml.c:847-920, when q41) as the ActQ blocks and, when given, the Wo matmul's
+// operand image (Q4_0: xm + xda; Q4_1: xm + xs41).  One 32-lane half-wave per token: 8 per pass.
+__device__ __forceinline__ void attn_pv_tail(const float * ob, int nt, int t0, int d0, int E, const ActQ & out, uint2 * xm,
+                                             float * xda, float * __restrict__ out_f32, int q41, uint4 * xs41) {
+    const int tid = threadIdx.x;
+    const int e = tid & 31;
+    const int nb = E / 32, blk = d0 / 32;
+    for (int t = tid >> 5; t < nt; t += 8) {
+        const float v = ob[t * 33 + e];
+        const int tok = t0 + t;
+        if (out_f32) out_f32[(size_t) tok * E + d0 + e] = v;
+        if (q41) {
+            // Q4_1 model: quantize_row_q4_1 (AVX2, ggml.c:847-920) of the block by the lane
+            // quad e < 4, written as the ActQ and (xs41 given) the Q4_1 MFMA operands (mm_mfma41.hip)
+            if (e < 4) {
+                float dd, mm;
+                uint32_t qword;
+                mv::q41_block_lds(ob + t * 33, e, dd, mm, qword);
+                mv::actq_store_block41(out, tok, blk, e, dd, mm, qword);
+                if (xs41) act41_emit(tok, nb, blk, e, qword, dd, mm, (uint4 *) xm, xs41);
+            }
+            continue;
+        }
+        float dd;
+        uint4 qs;
+        mv::q40_block32(v, tid, dd, qs);
+        if (e == 0) mv::actq_store_block(out, tok, blk, dd, qs);
+        if (xm && e < 4) {
+            // the masked MFMA fragment image of the Wo input (mm_common.h act40_emit): group
+            // c = e holds elements 8c..8c+7 = word c
+            const uint32_t word = e == 0 ? qs.x : e == 1 ? qs.y : e == 2 ? qs.z : qs.w;
+            act40_emit(tok, nb, blk, e, word, dd, xm, xda);
+        }
+    }
 }
 
 }  // namespace lvk

@@ -283,36 +283,7 @@ __global__ __launch_bounds__(256) void k_attn_p_pv(const uint16_t * __restrict__
             for (int b = 0; b < 4; ++b) ob[(4 * qt + b) * 33 + 4 * qd + a] = o[a][b];
     }
     __syncthreads();
-    // one 32-lane half-wave per token: 8 tokens per pass
-    const int e = tid & 31;
-    const int nb = E / 32, blk = d0 / 32;
-    for (int t = tid >> 5; t < nt; t += 8) {
-        const float v = ob[t * 33 + e];
-        const int tok = t0 + t;
-        if (out_f32) out_f32[(size_t) tok * E + d0 + e] = v;
-        if (q41) {
-            // Q4_1 model: quantize_row_q4_1 (AVX2, ggml.c:847-920) of the block by the lane
-            // quad e < 4, written as the ActQ and (xs41 given) the Q4_1 MFMA operands (mm_mfma41.hip)
-            if (e < 4) {
-                float dd, mm;
-                uint32_t qword;
-                mv::q41_block_lds(ob + t * 33, e, dd, mm, qword);
-                mv::actq_store_block41(out, tok, blk, e, dd, mm, qword);
-                if (xs41) act41_emit(tok, nb, blk, e, qword, dd, mm, (uint4 *) xm, xs41);
-            }
-            continue;
-        }
-        float dd;
-        uint4 qs;
-        mv::q40_block32(v, tid, dd, qs);
-        if (e == 0) mv::actq_store_block(out, tok, blk, dd, qs);
-        if (xm && e < 4) {
-            // the masked MFMA fragment image of the Wo input (mm_common.h act40_emit): group
-            // c = e holds elements 8c..8c+7 = word c
-            const uint32_t word = e == 0 ? qs.x : e == 1 ? qs.y : e == 2 ? qs.z : qs.w;
-            act40_emit(tok, nb, blk, e, word, dd, xm, xda);
-        }
-    }
+    attn_pv_tail(ob, nt, t0, d0, E, out, xm, xda, out_f32, q41, xs41);
 }
 
 }  // namespace

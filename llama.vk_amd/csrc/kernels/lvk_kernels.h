@@ -194,6 +194,7 @@ struct AttnLaunch {
     unsigned * err = nullptr; // host-mapped error word (DevError); kernels that spin report a timeout here
     int kv32 = 0;             // f32 K, V and queries (f16_kv = false): launch_attention only
     int seq_epochs = 0;       // decode attention: granule epoch = (sp->seq << 7) + epoch (no per-token zeroing)
+    int n_kv = 0;             // launch_attention_prompt_long: the host's copy of sp->n_past + n_tokens (0: unknown)
 };
 hipError_t launch_attention(const AttnLaunch & A, hipStream_t s);
 // prompt batches (N > 1, Q4_0 / Q4_1 output): scores+softmax per (head, pair of mirrored
@@ -204,6 +205,14 @@ struct ActImage;
 bool attention_prompt_supported(int n_embd, int n_head, int n_ctx);
 hipError_t launch_attention_prompt(const AttnLaunch & A, uint16_t * p_scratch, const ActImage & wo_image,
                                    hipStream_t s);
+// the same batches on contexts of up to 2048 positions (attention_prompt_long.hip): head_dim 128,
+// n_ctx % 32 == 0, 32 <= n_ctx <= 2048, the f16 cache; hipErrorNotSupported for anything else.
+// The scores workgroup's LDS rows are sized by A.n_kv (n_ctx when 0; a launch whose step block
+// holds more positions than that writes nothing), V and P stream through LDS in position tiles.
+// Same scratch, outputs and wo_image as launch_attention_prompt, bit for bit.
+bool attention_prompt_long_supported(int n_embd, int n_head, int n_ctx);
+hipError_t launch_attention_prompt_long(const AttnLaunch & A, uint16_t * p_scratch, const ActImage & wo_image,
+                                        hipStream_t s);
 // count into bad_d[0] / bad_d[1] the softmax arguments h <= 0 whose exp computed in
 // double / with the device expf differs from exp_tab[h]; 0 means that mode
 // reproduces the host table exactly

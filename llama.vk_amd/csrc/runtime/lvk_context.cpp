@@ -137,6 +137,7 @@ void Context::init(const llama_context_params & p) {
             cols_img = model.alloc(matvec_cols41_image_bytes((int) std::max(E, F), rows_cols41_max));
         prompt_exact = getenv("LVK_PROMPT_EXACT") && atoi(getenv("LVK_PROMPT_EXACT")) != 0;
         old_attention = getenv("LVK_ATTN_V1") && atoi(getenv("LVK_ATTN_V1")) != 0;
+        attn_long = !getenv("LVK_ATTN_LONG") || atoi(getenv("LVK_ATTN_LONG")) != 0;
         attn_gran = model.alloc(attention_decode_scratch_bytes((int) H, (int) C));
         LVK_HIP(hipMemset(attn_gran, 0, attention_decode_scratch_bytes((int) H, (int) C)));
         // granule tags (seq << 7) + layer + 1 stay unique per token with up to 126 layers
@@ -268,6 +269,18 @@ bool Context::use_batched(int n) const {
     return true;
 }
 
+// Which attention an n-token eval of consecutive positions runs.  Batches on the f16 cache take
+// attention_prompt.hip while its LDS windows hold n_ctx (<= 1024) and attention_prompt_long.hip
+// beyond (<= 2048; LVK_ATTN_LONG=0 at context creation: the generic kernel instead); a single
+// token the decode kernels; everything else (the f32 cache, other head sizes) attention.hip.
+int Context::prompt_attn_path(int n) const {
+    const int E = (int) model.hp.n_embd, H = (int) model.hp.n_head;
+    if (n == 1) return !old_attention && !kv32 && attention_decode_supported(E, H, n_ctx) ? 3 : 0;
+    if (kv32) return 0;
+    if (attention_prompt_supported(E, H, n_ctx)) return 1;
+    return attn_long && attention_prompt_long_supported(E, H, n_ctx) ? 2 : 0;
+}
+
 // The layer sequence, the same for every weight type (f16 weights:
 // ggml_compute_forward_mul_mat_f16_f32 where the Q4 types run mul_mat_q_f32; the activations are
 // converted to f16 where the Q4 types quantize them; f32 weights: ggml_compute_forward_mul_mat_f32
@@ -291,8 +304,10 @@ void Context::enqueue_forward(const Forward & f) {
     const int qt = model.qtype;
     const bool cols = rows && rows_cols(n);
     const bool batched = !cols && use_batched(n);
-    const bool prompt_attn = !rows && n > 1 && !kv32 && attention_prompt_supported(E, H, n_ctx);
-    const bool decode_attn = !rows && n == 1 && !old_attention && !kv32 && attention_decode_supported(E, H, n_ctx);
+    // path 1 or 2: one of the two prompt pairs, which write the Wo operand themselves
+    const int attn_path = rows ? 0 : prompt_attn_path(n);
+    const bool prompt_attn = attn_path == 1 || attn_path == 2;
+    const bool decode_attn = attn_path == 3;
     if (decode_attn && !seq_epochs)
         // the decode attention's score granules carry epoch = layer + 1: zero them once per token
         LVK_HIP(hipMemsetAsync(attn_gran, 0, attention_decode_scratch_bytes(H, n_ctx), stream));
@@ -332,6 +347,13 @@ void Context::enqueue_forward(const Forward & f) {
         at.err = err_d;
         at.kv32 = kv32;
         at.seq_epochs = seq_epochs ? 1 : 0;
+        at.n_kv = f.n_kv;
+        auto prompt_attention = [&](const ActImage & wo) {
+            timed_launch(K_ATTN, 0, [&] {
+                return attn_path == 2 ? launch_attention_prompt_long(at, (uint16_t *) scores, wo, stream)
+                                      : launch_attention_prompt(at, (uint16_t *) scores, wo, stream);
+            });
+        };
         // a batched decode step: RoPE + KV append per row from qkv32, then all rows' attention
         const size_t layer_off = il * (size_t) n_ctx * E;
         auto rows_rope_attn = [&] {
@@ -379,9 +401,7 @@ void Context::enqueue_forward(const Forward & f) {
             if (rows)
                 rows_rope_attn();
             else if (prompt_attn)
-                timed_launch(K_ATTN, 0, [&] {
-                    return launch_attention_prompt(at, (uint16_t *) scores, wo_fused ? img : ActImage{}, stream);
-                });
+                prompt_attention(wo_fused ? img : ActImage{});
             else
                 timed_launch(K_ATTN, 0, [&] { return launch_attention(at, stream); });
             in = img;
@@ -409,7 +429,7 @@ void Context::enqueue_forward(const Forward & f) {
         if (rows)
             rows_rope_attn();
         else if (prompt_attn)
-            timed_launch(K_ATTN, 0, [&] { return launch_attention_prompt(at, (uint16_t *) scores, ActImage{}, stream); });
+            prompt_attention(ActImage{});
         else if (decode_attn)
             timed_launch(K_ATTN, 0, [&] { return launch_attention_decode(at, attn_gran, (unsigned) il + 1, stream); });
         else
@@ -723,6 +743,7 @@ void Context::begin_eval(const int * tokens, int n, int n_past, const EvalPart &
         f.tok_src = tok_d + part.tok_off;
         f.logit_row = last_only ? 0 : part.tok_off;
         f.head = part.head;
+        f.n_kv = n_past + n;
         enqueue_forward(f);
         if (part.score) {
             enqueue_score(n, part.score_argmax);

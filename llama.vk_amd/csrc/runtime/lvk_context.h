@@ -84,6 +84,7 @@ struct Context {
     // bit-faithful VALU kernels (prompt_exact; env LVK_PROMPT_EXACT=1)
     bool prompt_exact = false;
     bool old_attention = false;  // env LVK_ATTN_V1=1: single-token evals on the one-kernel attention.hip
+    bool attn_long = true;       // env LVK_ATTN_LONG=0: contexts past attention_prompt.hip's window keep the generic kernel
     void * attn_gran = nullptr;  // [H][n_ctx] {tag, score} granules of the decode attention
     // batched (N > 1) matmuls: the operand image of the matrix about to run (lvk_kernels.h
     // ActImage, sized for n_ctx rows of max(E, F)), rewritten before every matmul
@@ -266,6 +267,7 @@ struct Context {
         bool embed = true;              // run the embedding (false: x holds the rows already)
         bool rows = false;              // the tokens are a batched decode step's rows (rows_d / slots_d), not
                                         //   n consecutive positions of slot 0
+        int n_kv = 0;                   // the host's n_past + n of an eager slice (0: not known here)
     };
     static Forward rows_forward(int n) {      // a batched decode step over n rows, every row's logits
         Forward f;
@@ -275,6 +277,9 @@ struct Context {
         return f;
     }
     void enqueue_forward(const Forward & f);
+    // the attention of an n-token non-rows eval (lvk_prompt_attn_path): 0 attention.hip, 1
+    // attention_prompt.hip, 2 attention_prompt_long.hip, 3 attention_decode.hip
+    int prompt_attn_path(int n) const;
     bool use_batched(int n) const;
     // a rows step of n rows takes launch_matvec_cols for its matmuls (ahead of use_batched and the
     // generic matvecs)

@@ -283,10 +283,27 @@ int lvk_attention_q(int kind, int type, const uint16_t * kc, const uint16_t * vc
     return attention_impl(kc, vc, q, n_embd, n_head, n_ctx, n_past, n, out, nullptr, kind, type, blocks);
 }
 
+int lvk_attention_long(int type, const uint16_t * kc, const uint16_t * vc, const float * q, int n_embd, int n_head,
+                       int n_ctx, int n_past, int n, float * out, void * blocks) {
+    if (type != lvk::Q4_0 && type != lvk::Q4_1) return fail(__func__, "type: 2 (Q4_0) or 3 (Q4_1)");
+    if (!kc || !vc || !q || !out) return fail(__func__, "null argument");
+    if (!lvk::attention_prompt_long_supported(n_embd, n_head, n_ctx))
+        return fail(__func__, "needs head_dim 128, n_ctx % 32 == 0, 32 <= n_ctx <= 2048");
+    if (n < 1 || n > n_ctx || n_past < 0 || n_past > n_ctx - n) return fail(__func__, "need n >= 1 and 0 <= n_past <= n_ctx - n");
+    return attention_impl(kc, vc, q, n_embd, n_head, n_ctx, n_past, n, out, nullptr, 3, type, blocks);
+}
+
+int lvk_prompt_attn_path(struct llama_context * ctx, int n) {
+    if (!ctx || n < 1) return -1;
+    return ctx->stages().front()->prompt_attn_path(n);
+}
+
+// kind 3: the long-context prompt kernels (lvk_attention_long)
 static int attention_impl(const uint16_t * kc, const uint16_t * vc, const float * q, int n_embd, int n_head,
                           int n_ctx, int n_past, int n, float * out, float * scores_out, int kind, int type,
                           void * blocks) {
-    const char * fn = kind == 1 ? "lvk_attention_prompt" : kind == 2 ? "lvk_attention_decode" : "lvk_attention";
+    const char * fn = kind == 1 ? "lvk_attention_prompt" : kind == 2 ? "lvk_attention_decode"
+                    : kind == 3 ? "lvk_attention_long" : "lvk_attention";
     try {
         lvk::Scratch dv;
         const size_t CE = (size_t) n_ctx * n_embd;
@@ -311,7 +328,9 @@ static int attention_impl(const uint16_t * kc, const uint16_t * vc, const float 
         uint16_t * pd = nullptr;
         if (scores_out) pd = (uint16_t *) dv.get((size_t) n * n_head * n_ctx * 2);
         A.p16_out = pd;
+        A.n_kv = n_past + n;
         if (kind == 1) LVK_HIP(lvk::launch_attention_prompt(A, (uint16_t *) A.scores, lvk::ActImage{}, nullptr));
+        else if (kind == 3) LVK_HIP(lvk::launch_attention_prompt_long(A, (uint16_t *) A.scores, lvk::ActImage{}, nullptr));
         else if (kind == 2) {
             void * gran = dv.get(lvk::attention_decode_scratch_bytes(n_head, n_ctx));
             LVK_HIP(hipMemset(gran, 0, lvk::attention_decode_scratch_bytes(n_head, n_ctx)));

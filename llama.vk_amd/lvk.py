@@ -117,6 +117,8 @@ _sig("lvk_attention_prompt", C.c_int, [u16p, u16p, f32p, C.c_int, C.c_int, C.c_i
 _sig("lvk_attention_decode", C.c_int, [u16p, u16p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, f32p])
 _sig("lvk_attention_scores", C.c_int, [u16p, u16p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, f32p])
 _sig("lvk_attention_q", C.c_int, [C.c_int, C.c_int, u16p, u16p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, u8p])
+_sig("lvk_attention_long", C.c_int, [C.c_int, u16p, u16p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, u8p])
+_sig("lvk_prompt_attn_path", C.c_int, [C.c_void_p, C.c_int])
 _sig("lvk_rope_kv_rows", C.c_int, [f32p, i32p, i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                    u16p, u16p, u16p])
 _sig("lvk_attention_rows", C.c_int, [C.c_int, u16p, u16p, C.c_int, C.c_int, C.c_int, f32p, i32p, i32p, C.c_int, C.c_int,
@@ -528,6 +530,11 @@ class Llama:
         """prompt batches on the bit-faithful VALU path (True) or the MFMA path (False, default)"""
         lib.lvk_set_prompt_exact(self.ctx, int(on))
 
+    def prompt_attn_path(self, n):
+        """the attention an n-token eval runs: 0 attention.hip, 1 attention_prompt.hip, 2
+        attention_prompt_long.hip, 3 the decode kernels (lvk_prompt_attn_path)"""
+        return lib.lvk_prompt_attn_path(self.ctx, int(n))
+
     def reset_profile(self):
         lib.lvk_reset_profile(self.ctx)
 
@@ -700,6 +707,17 @@ def attention_q(kind, qtype, kc, vc, q, n_embd, n_head, n_ctx, n_past, n):
     _check(lib.lvk_attention_q(kind, qtype, np.ascontiguousarray(kc, np.uint16).ravel(),
                                np.ascontiguousarray(vc, np.uint16).ravel(), np.ascontiguousarray(q, np.float32).ravel(),
                                n_embd, n_head, n_ctx, n_past, n, out, blocks), "lvk_attention_q")
+    return out.reshape(n, n_embd), blocks.reshape(n, -1)
+
+
+def attention_long(qtype, kc, vc, q, n_embd, n_head, n_ctx, n_past, n):
+    """lvk_attention_long: attention_q through the long-context prompt kernels (attention_prompt_long.hip,
+    n_ctx <= 2048); returns (out [n][n_embd] f32, blocks [n][n_embd/32 * block bytes] uint8)"""
+    out = np.zeros(n * n_embd, np.float32)
+    blocks = np.zeros(n * (n_embd // 32) * BLOCK_BYTES.get(qtype, 24), np.uint8)
+    _check(lib.lvk_attention_long(qtype, np.ascontiguousarray(kc, np.uint16).ravel(),
+                                  np.ascontiguousarray(vc, np.uint16).ravel(), np.ascontiguousarray(q, np.float32).ravel(),
+                                  n_embd, n_head, n_ctx, n_past, n, out, blocks), "lvk_attention_long")
     return out.reshape(n, n_embd), blocks.reshape(n, -1)
 
 
