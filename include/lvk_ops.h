@@ -204,8 +204,9 @@ LVK_API int lvk_embed_rows(int type, const void * emb, int n_vocab, int n_embd, 
 /* The batched decode step's matmul (matvec_cols.hip, launch_matvec_cols) on host data: weights in
  * file layout, f32 rows in, results out, with the bits of the lvk_layer_* entries above.  These are
  * entries of their own: lvk_layer_* and its paths 0..3 stay as they are (path 0 keeps meaning the
- * choice of a non-rows eval, and no path 4 or 5 exists).  Q4_0 (type 2) only, k 4096 or 11008
- * (lvk_cols_resid) / 4096 (the other two), 2 <= n <= 4096, rows % 8 == 0.  Every argument is checked
+ * choice of a non-rows eval, and no path 4 or 5 exists).  Q4_0 (type 2) only; k an n_embd (4096, or
+ * 5120 / 6656 / 8192 on matvec_cols_long.hip) for all three, an n_ff (11008, or 13824 / 17920 / 22016)
+ * for lvk_cols_resid only; 2 <= n <= 4096, rows % 8 == 0.  Every argument is checked
  * before anything is uploaded; an unsupported (type, k, n) returns -1 with a message and writes
  * nothing.
  *   lvk_cols_store   y[t] = W . quant(g * rms_norm(x[t])), w [m][k], x [n][k], y [n][m] out
@@ -229,9 +230,10 @@ LVK_API int lvk_cols41_swiglu(const void * w1, const void * w3, int f, int k, co
                               float * u_out);
 
 /* 1 when a batched decode step (lvk_decode_batch and its chain / sample / score forms) of n rows
- * on this context runs its matmuls through matvec_cols.hip or matvec_cols41.hip, else 0: a Q4_0
- * model whose matrices have row lengths 4096 / 11008, or a Q4_1 model with 4096 / 11008 or 5120 /
- * 13824, 2 <= n <= the type's measured limit (lvk_context.cpp rows_cols_max, rows_cols41_max), and
+ * on this context runs its matmuls through matvec_cols.hip / matvec_cols_long.hip or
+ * matvec_cols41.hip, else 0: a Q4_0 model whose matrices have row lengths 4096 / 11008, 5120 / 13824,
+ * 6656 / 17920 or 8192 / 22016, or a Q4_1 model with 4096 / 11008 or 5120 / 13824, 2 <= n <= the
+ * measured limit of the type and shape (lvk_context.cpp rows_cols_max, rows_cols41_max), and
  * not env LVK_ROWS_COLS=0 (read once per process). */
 LVK_API int lvk_rows_cols_active(struct llama_context * ctx, int n);
 

@@ -159,6 +159,8 @@ int cu_count();
 // y / u are [n][M] / [n][M/2] as launch_matvec writes them, bit for bit.  Q4_0, K 4096 (EPI_STORE,
 // EPI_RESID, EPI_SWIGLU_F32) or 11008 (EPI_RESID), M % 8 == 0, n >= 2, tok0 == 0; the pairs
 // (PRO_NORM, EPI_STORE), (PRO_ACTQ, EPI_RESID), (PRO_ACTF, EPI_RESID), (PRO_NORM, EPI_SWIGLU_F32).
+// The row lengths of LLaMA 13B / 30B / 65B go to matvec_cols_long.hip (one kernel for any chunk count, tiles of
+// 16 / 12 / 10 columns): K 5120, 6656, 8192 with the pairs of 4096, K 13824, 17920, 22016 with those of 11008.
 // The step's rows are converted once into L.cols_img (matvec_cols_image_bytes(K, n) bytes) by a
 // launch of its own.  hipErrorNotSupported for anything else: the caller keeps its route.
 bool matvec_cols_supported(int qtype, int K, int n);

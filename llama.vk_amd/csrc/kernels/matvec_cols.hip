@@ -32,31 +32,15 @@
 #include "lvk_device.h"
 #include "lvk_kernels.h"
 #include "matvec_common.h"
+#include "matvec_cols_common.h"
 
 namespace lvk {
 
 namespace {
 using namespace mv;
+using namespace cols;
 
-struct ColsParams : MvArgs {
-    const uint4 * nib;
-    const float4 * scl;
-    const uint4 * img;          // the packed column image (k_cols_act), column t at t * CS16
-    int G;                      // row groups (M / 8)
-    int M;                      // rows: the column stride of y (u: M / 2)
-    int col0, ncols;            // this launch's columns [col0, col0 + ncols)
-};
-
-// per-wave block-scale slice (8 rows x 32 blocks), row stride padded as in matvec_cu.hip: the
-// per-row broadcast float4 reads are bank-conflict free
-constexpr int SRS = 40, SPL = 8 * SRS;
-
-// packed column image / LDS table of one column of K = 32 nb elements, in uint4 units:
-//   [nb]     nibbles: uint4 (8 u + j), u < nb / 8, chain j: word k = a(8u + 2k, j) | a(8u + 2k + 1, j) << 16,
-//            a(i, j) = the signed nibbles of elements 4j .. 4j + 3 of block i (16 bits)
-//   [NC * 8] dx: float [c][j][m] = dx of block 32 c + 8 m + j (0 past the row's end)
-__host__ __device__ constexpr int cols_stride16(int K) { return K / 32 + (K / 32 + 31) / 32 * 8; }
-
+// the packed column image (matvec_cols_common.h): the stores of one block's nibble group and dx
 __device__ __forceinline__ void cols_store16(uint16_t * p16, int i, int j, uint32_t v) {
     p16[(size_t) (((i >> 3) * 8 + j) * 8 + (i & 7))] = (uint16_t) v;
 }
@@ -406,9 +390,10 @@ hipError_t go(const ColsParams & P, int n, hipStream_t s) {
 
 }  // namespace
 
-// row lengths compiled in: n_embd and n_ff of LLaMA 7B
+// row lengths compiled in: n_embd and n_ff of LLaMA 7B; those of 13B, 30B and 65B go to
+// matvec_cols_long.hip
 bool matvec_cols_supported(int qtype, int K, int n) {
-    return qtype == Q4_0 && (K == 4096 || K == 11008) && n >= 2;
+    return qtype == Q4_0 && (K == 4096 || K == 11008 || cols_long_supported(K)) && n >= 2;
 }
 
 hipError_t launch_matvec_cols(const MvLaunch & L, int pro, int epi, hipStream_t s) {
@@ -416,7 +401,7 @@ hipError_t launch_matvec_cols(const MvLaunch & L, int pro, int epi, hipStream_t 
     if (!matvec_cols_supported(L.w.qtype, K, n) || L.w.M % 8 || L.tok0 != 0) return hipErrorNotSupported;
     const bool pair = (pro == PRO_NORM && (epi == EPI_STORE || epi == EPI_SWIGLU_F32)) ||
                       ((pro == PRO_ACTQ || pro == PRO_ACTF) && epi == EPI_RESID);
-    if (!pair || (K == 11008 && epi != EPI_RESID)) return hipErrorNotSupported;
+    if (!pair || (K > 8192 && epi != EPI_RESID)) return hipErrorNotSupported;     // an n_ff: the W2 role only
     if (!mv_inputs_set(L, pro) || !L.cols_img || !L.w.nib || !L.w.scl) return hipErrorInvalidValue;
     if (epi == EPI_SWIGLU_F32 ? (!L.u || !L.silu_tab) : !L.y) return hipErrorInvalidValue;
     ColsParams P{};
@@ -438,6 +423,7 @@ hipError_t launch_matvec_cols(const MvLaunch & L, int pro, int epi, hipStream_t 
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     ev.last();
+    if (cols_long_supported(K)) return launch_cols_long(P, K, epi, n, s);
     if (K == 4096) {
         switch (epi) {
             case EPI_STORE: return go<EPI_STORE, 4096>(P, n, s);

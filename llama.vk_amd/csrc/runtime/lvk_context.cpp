@@ -28,7 +28,23 @@ namespace lvk {
 // spread (profiles/rows_cols_speed.json: 7B Q4_0, step ms new / old at S = 2, 4, 8, 16, 17, 24:
 // 2.30 / 3.14, 2.86 / 3.66, 3.57 / 5.75, 5.44 / 7.92, 6.87 / 8.23, 8.18 / 8.51; at 32, 48 and 64 the
 // MFMA matmuls win, 9.41 / 8.85, 13.38 / 10.68 and 17.35 / 11.52; 25..31 were not measured)
-constexpr int rows_cols_max = 24;
+// The limit is per shape (n_embd): the 13B / 30B / 65B shapes run on matvec_cols_long.hip, measured the same way and
+// held to the same rule (profiles/rows_cols_long_speed.json: the shapes cut to 8 layers, step ms new / old;
+// 13B at S = 2, 4, 8, 16: 0.78 / 1.75, 0.98 / 1.93, 1.48 / 3.27, 2.42 / 2.48, and 2.93 / 2.67 at 17;
+// 30B at 2, 4, 8, 12, 13, 15: 1.04 / 3.25, 1.34 / 3.62, 2.14 / 6.07, 3.26 / 8.57, 3.45 / 10.55, 3.54 / 10.81, and
+// 3.56 / 3.55 at 16; 65B at 2, 4, 8, 10, 11, 15: 1.26 / 3.91, 1.61 / 4.36, 2.52 / 8.12, 4.00 / 11.50, 4.24 / 11.73,
+// 4.56 / 15.25, and 4.60 / 4.41 at 16: from 16 rows on the old route is the MFMA matmuls, which win at 17, 24 and 32
+// everywhere.  Spreads are 0.003 .. 0.11 ms; 13B at 16 wins by 0.061 ms against 2 x 0.022.  13B at 3, 5..7 and
+// 9..15 was not measured: DESIGN.md)
+constexpr int rows_cols_max(int E) {
+    switch (E) {
+        case 4096: return 24;
+        case 5120: return 16;
+        case 6656: return 15;
+        case 8192: return 15;
+    }
+    return 0;
+}
 // the same for a Q4_1 model on matvec_cols41.hip, by the same rule (profiles/rows_cols41_speed.json:
 // 13B-shaped Q4_1, step ms new / old at S = 2, 4, 8, 12, 15, 16, 17: 4.75 / 8.04, 6.56 / 13.85,
 // 10.84 / 23.72, 17.52 / 34.30, 18.67 / 42.96, 18.64 / 21.06, 21.71 / 23.18; at 24 and 32 the MFMA
@@ -132,7 +148,8 @@ void Context::init(const llama_context_params & p) {
         if (model.qtype == F16 || model.qtype == F32) attn_f32 = (float *) model.alloc(C * E * 4);
         qkv32 = (float *) model.alloc(C * 3 * E * 4);
         uf = (float *) model.alloc(C * F * 4);
-        if (model.qtype == Q4_0) cols_img = model.alloc(matvec_cols_image_bytes((int) std::max(E, F), rows_cols_max));
+        if (model.qtype == Q4_0 && rows_cols_max((int) E) > 0)
+            cols_img = model.alloc(matvec_cols_image_bytes((int) std::max(E, F), rows_cols_max((int) E)));
         if (model.qtype == Q4_1 && matvec_cols41_supported((int) E, 2) && matvec_cols41_supported((int) F, 2))
             cols_img = model.alloc(matvec_cols41_image_bytes((int) std::max(E, F), rows_cols41_max));
         prompt_exact = getenv("LVK_PROMPT_EXACT") && atoi(getenv("LVK_PROMPT_EXACT")) != 0;
@@ -238,8 +255,8 @@ static double qbytes(const QMatrix & w) {
     return (double) w.M * (w.K / 32) * (w.qtype == Q4_0 ? 20 : 24);
 }
 
-// A batched decode step of 2..rows_cols_max rows runs its matmuls on matvec_cols.hip: a Q4_0 model
-// whose four layer matrices and lm_head that file has row lengths for; a Q4_1 model likewise on
+// A batched decode step of 2..rows_cols_max(n_embd) rows runs its matmuls on matvec_cols.hip / matvec_cols_long.hip:
+// a Q4_0 model whose four layer matrices and lm_head those files have row lengths for; a Q4_1 model likewise on
 // matvec_cols41.hip, up to rows_cols41_max rows.  LVK_ROWS_COLS=0 (read once per process) keeps the
 // step on the routes below, for A/B runs.
 bool Context::rows_cols(int n) const {
@@ -248,7 +265,7 @@ bool Context::rows_cols(int n) const {
     if (!on || !cols_img || n < 2 || !model.has_head || !model.has_embed) return false;
     if (qt == Q4_1) {
         if (n > rows_cols41_max ||!matvec_cols41_supported(E, n) || !matvec_cols41_supported(F, n) || E > 5120 || F < 11008) return false;
-    } else if (n > rows_cols_max || !matvec_cols_supported(qt, E, n) || !matvec_cols_supported(qt, F, n)) {
+    } else if (n > rows_cols_max(E) || !matvec_cols_supported(qt, E, n) || !matvec_cols_supported(qt, F, n) || E > 8192 || F < 11008) {
         return false;
     }
     auto fits = [&](const QMatrix & w, int K) { return w.qtype == qt && w.K == K && w.M % 8 == 0; };

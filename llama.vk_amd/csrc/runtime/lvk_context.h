@@ -98,7 +98,7 @@ struct Context {
     float * uf = nullptr;        // [C][F] silu(w1 x) * (w3 x)
     // a batched decode step of a Q4_0 model through matvec_cols.hip, or of a Q4_1 model through
     // matvec_cols41.hip (rows_cols): the step's packed column image, rewritten before every matmul
-    void * cols_img = nullptr;   // [rows_cols_max] (Q4_1: [rows_cols41_max]) columns of max(E, F)
+    void * cols_img = nullptr;   // [rows_cols_max(E)] (Q4_1: [rows_cols41_max]) columns of max(E, F)
     // f16 and f32 models only: the attention's f32 output, the Wo input (F16: converted to f16
     // by launch_act / the matvec's prologue; F32: read as it is); nullptr = Wo takes the
     // quantized aq_attn

@@ -740,7 +740,7 @@ static const char * cols_args_bad(int type, int rows, int k, int n) {
     if (k < 256 || k % 256) return "k must be a positive multiple of 256";
     if (n < 1 || n > 4096) return "n must be in 1..4096";
     if (rows < 8 || rows % 8 || rows > (1 << 20)) return "the matrix needs a multiple of 8 rows";
-    if (!lvk::matvec_cols_supported(type, k, n)) return "matvec_cols.hip takes Q4_0, k 4096 or 11008, n >= 2";
+    if (!lvk::matvec_cols_supported(type, k, n)) return "the Q4_0 columns kernels take k 4096, 5120, 6656, 8192 (n_embd) or 11008, 13824, 17920, 22016 (n_ff), n >= 2";
     return nullptr;
 }
 
@@ -748,7 +748,7 @@ int lvk_cols_store(int type, const void * w, int m, int k, const float * g, cons
     try {
         if (!w || !g || !x || !y) return fail(__func__, "null argument");
         if (const char * bad = cols_args_bad(type, m, k, n)) return fail(__func__, bad);
-        if (k != 4096) return fail(__func__, "EPI_STORE is compiled in for k 4096");
+        if (k > 8192) return fail(__func__, "EPI_STORE is compiled in for the n_embd row lengths");
         lvk::Scratch dv;
         lvk::MvLaunch a;
         a.w = layer_matrix(dv, type, w, m, nullptr, 0, k, 0, false);
@@ -793,7 +793,7 @@ int lvk_cols_swiglu(int type, const void * w1, const void * w3, int f, int k, co
         if (!w1 || !w3 || !g || !x || !u_out) return fail(__func__, "null argument");
         if (f < 4 || f % 4 || f > (1 << 19)) return fail(__func__, "the interleaved W1|W3 image needs f % 4 == 0");
         if (const char * bad = cols_args_bad(type, 2 * f, k, n)) return fail(__func__, bad);
-        if (k != 4096) return fail(__func__, "EPI_SWIGLU_F32 is compiled in for k 4096");
+        if (k > 8192) return fail(__func__, "EPI_SWIGLU_F32 is compiled in for the n_embd row lengths");
         lvk::Scratch dv;
         lvk::MvLaunch c;
         c.w = layer_matrix(dv, type, w1, f, w3, f, k, 1, false);

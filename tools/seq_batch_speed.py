@@ -12,6 +12,8 @@ record per model to the JSON file (default profiles/seq_batch_speed.json) and pr
 --sweep S,S,...: these step sizes instead; --profile-at S,S,...: the per-class profile at these;
 --argmax-only: skip the logits-to-host leg (the A/B legs of profiles/rows_cols41_speed.json: one
 process per leg and repeat, LVK_ROWS_COLS=0 for the old route).
+--layers N: the model cut to its first N layers (a file of its own), where the whole one takes too
+long to write; the record's model name says so.
 --chain [--repeats R] [--parent FILE ...]: the chained leg instead (run_chain): lvk_decode_batch_chain
 against the host-fed legs, every leg R times, into profiles/seq_chain_speed.json; FILEs are records
 this tool wrote at the parent commit.
@@ -30,7 +32,11 @@ import lvk
 
 CFG = {'7b': ('llama-7b-q4_0.bin', dict(n_embd=4096, n_head=32, n_layer=32, ftype=2, seed=1)),
        '13b': ('llama-13b-q4_1.bin', dict(n_embd=5120, n_head=40, n_layer=40, ftype=3, seed=2)),
-       '7b-f16': ('llama-7b-f16.bin', dict(n_embd=4096, n_head=32, n_layer=32, ftype=1, seed=1))}
+       '7b-f16': ('llama-7b-f16.bin', dict(n_embd=4096, n_head=32, n_layer=32, ftype=1, seed=1)),
+       # the Q4_0 shapes of matvec_cols_long.hip (profiles/rows_cols_long_speed.json)
+       '13b-q4_0': ('llama-13b-q4_0.bin', dict(n_embd=5120, n_head=40, n_layer=40, ftype=2, seed=4)),
+       '30b': ('llama-30b-q4_0.bin', dict(n_embd=6656, n_head=52, n_layer=60, ftype=2, seed=5)),
+       '65b': ('llama-65b-q4_0.bin', dict(n_embd=8192, n_head=64, n_layer=80, ftype=2, seed=3))}
 N_CTX = 512
 N_SLOT = 64
 
@@ -53,8 +59,10 @@ def median_ms(fn, steps, warm=3):
     return float(np.median(ts)) * 1e3
 
 
-def run(name, steps, sweep=None, profile_at=(16,), argmax_only=False):
+def run(name, steps, sweep=None, profile_at=(16,), argmax_only=False, layers=0):
     fn, cfg = CFG[name]
+    if layers:
+        fn, cfg, name = fn.replace('.bin', '-l%d.bin' % layers), dict(cfg, n_layer=layers), '%s %d layers' % (name, layers)
     path = os.path.join('/tmp/lvk_bench', fn)
     if not os.path.exists(path):
         os.makedirs(os.path.dirname(path), exist_ok=True)
@@ -281,7 +289,7 @@ def run_sample(name, steps, repeats):
 
 def main():
     args = sys.argv[1:]
-    steps, out, sweep, profile_at, argmax_only = 20, None, None, (16,), False
+    steps, out, sweep, profile_at, argmax_only, layers = 20, None, None, (16,), False, 0
     names, chain, repeats, parents, sample = [], False, 3, [], False
     while args:
         a = args.pop(0)
@@ -295,6 +303,8 @@ def main():
             profile_at = tuple(int(v) for v in args.pop(0).split(','))
         elif a == '--argmax-only':
             argmax_only = True
+        elif a == '--layers':
+            layers = int(args.pop(0))
         elif a == '--chain':
             chain = True
         elif a == '--sample':
@@ -311,7 +321,7 @@ def main():
     for name in names or ['7b']:
         rec = (run_sample(name, steps, repeats) if sample else
                run_chain(name, steps, repeats, parents) if chain else
-               run(name, steps, sweep, profile_at, argmax_only))
+               run(name, steps, sweep, profile_at, argmax_only, layers))
         recs = [r for r in recs if r['model'] != rec['model']] + [rec]
         print(json.dumps(rec), flush=True)
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
