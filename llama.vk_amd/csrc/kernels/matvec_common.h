@@ -10,6 +10,10 @@ namespace lvk {
 // the Q4_1 half of matvec_cu_supported / launch_matvec_cu (matvec_cu41.hip)
 bool matvec_cu41_supported(int K);
 hipError_t launch_matvec_cu41(const MvLaunch & L, int pro, int epi, hipStream_t s);
+// the Q4_0 row lengths of LLaMA 13B / 30B (matvec_cu_long.hip: 5120 / 13824, 6656 / 17920; none with
+// env LVK_DECODE_LONG=0)
+bool matvec_cu_long_supported(int K);
+hipError_t launch_matvec_cu_long(const MvLaunch & L, int pro, int epi, hipStream_t s);
 
 namespace mv {
 

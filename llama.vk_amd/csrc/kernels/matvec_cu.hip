@@ -421,12 +421,12 @@ int cu_count() {
 #ifdef LVK_PROBE_TIMING
 void * lvk_probe_trace() { void * p = nullptr; (void) hipGetSymbolAddress(&p, HIP_SYMBOL(g_trace)); return p; }
 #endif
-// row lengths compiled in: the LLaMA 7B/13B-free Q4_0 shapes (n_embd 4096 / 8192,
-// n_ff 11008 / 22016; llama.cpp:771-779)
+// row lengths compiled in: the LLaMA 7B and 65B Q4_0 shapes here (n_embd 4096 / 8192, n_ff 11008 /
+// 22016; llama.cpp:771-779), the 13B and 30B ones in matvec_cu_long.hip
 bool matvec_cu_supported(int K, int qtype) {
     if (qtype == Q4_1) return matvec_cu41_supported(K);
     if (qtype == F16 || qtype == F32) return true;      // matvec_f16.hip / matvec_f32.hip take every row length
-    return K == 4096 || K == 11008 || K == 8192 || K == 22016;
+    return K == 4096 || K == 11008 || K == 8192 || K == 22016 || matvec_cu_long_supported(K);
 }
 
 hipError_t launch_matvec_cu(const MvLaunch & L, int pro, int epi, hipStream_t s) {
@@ -434,6 +434,7 @@ hipError_t launch_matvec_cu(const MvLaunch & L, int pro, int epi, hipStream_t s)
     if (L.w.qtype == F16) return launch_matvec_f16(L, pro, epi, s);
     if (L.w.qtype == F32) return launch_matvec_f32(L, pro, epi, s);
     if (L.w.qtype != Q4_0 || L.n_tokens != 1 || L.w.M % 8) return hipErrorNotSupported;
+    if (matvec_cu_long_supported(L.w.K)) return launch_matvec_cu_long(L, pro, epi, s);
     if (!mv_inputs_set(L, pro)) return hipErrorInvalidValue;
     CuParams P{};
     mv_fill(P, L, true);

@@ -274,6 +274,22 @@ bool Context::rows_cols(int n) const {
     return fits(model.output, E);
 }
 
+// A single-token eval runs every matrix on the CU-balanced decode kernels (or the one f16 / f32 matvec): both
+// row lengths of the model are compiled in for its type (matvec_cu_supported; for Q4_0 13B / 30B not with
+// env LVK_DECODE_LONG=0) and every matrix is whole row groups.  enqueue_forward's single-token branch
+// follows the same two tests through launch_matvec_auto and ffn_f32.  matvec_cu_supported does not know the
+// role: matvec_cu_long.hip has the n_embd roles at 5120 / 6656 and the n_ff roles at 13824 / 17920 only, so
+// a model with n_embd 13824 would report 1 while its QKV takes the generic kernel.  No LLaMA file has such a
+// shape (n_ff follows from n_embd).
+bool Context::decode_cu() const {
+    const int E = (int) model.hp.n_embd, F = (int) model.hp.n_ff(), qt = model.qtype;
+    if (!matvec_cu_supported(E, qt) || !matvec_cu_supported(F, qt)) return false;
+    auto fits = [&](const QMatrix & w, int K) { return w.qtype == qt && w.K == K && w.M >= 8 && w.M % 8 == 0; };
+    for (const Layer & ly : model.layers)
+        if (!fits(ly.wqkv, E) || !fits(ly.wo, E) || !fits(ly.w13, E) || !fits(ly.w2, F)) return false;
+    return !model.has_head || fits(model.output, E);
+}
+
 // batches go through the batched matmuls (launch_act + launch_mm) when every matrix of the
 // model fits them: f16 and f32 weights from 2 tokens on (their matvec is single-token only), the Q4
 // types from 16 (the MFMA tile is 16 tokens wide; below that the per-row VALU kernels win)

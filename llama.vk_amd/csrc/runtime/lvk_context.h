@@ -284,6 +284,8 @@ struct Context {
     // a rows step of n rows takes launch_matvec_cols for its matmuls (ahead of use_batched and the
     // generic matvecs)
     bool rows_cols(int n) const;
+    // a single-token eval runs every matrix through launch_matvec_cu (lvk_decode_cu_active)
+    bool decode_cu() const;
     void build_graph(DecodeGraph kind);
     int eval_greedy(int token, int n_past);
     void kv_get();

@@ -95,7 +95,8 @@ static int mul_mat_impl(int type, const void * w, int m, int k, const float * g,
     float * xd = dv.up(x, (size_t) n * k);
     if (type == lvk::Q4_1 || norm || (n == 1 && lvk::matvec_cu_supported(k, type))) {
         // the kernel quantizes the f32 input in its prologue: every Q4_1 kernel, the Q4_0 norm
-        // kernels, and the Q4_0 single-column decode kernel (matvec_cu.hip) where compiled in
+        // kernels, and the Q4_0 single-column decode kernels (matvec_cu.hip, matvec_cu_long.hip) where
+        // compiled in
         L.x = xd;
         if (norm) L.g = dv.up(g, (size_t) k);
         LVK_HIP(lvk::launch_matvec_auto(L, norm ? lvk::PRO_NORM : lvk::PRO_ACTF, lvk::EPI_STORE, nullptr));
@@ -1000,6 +1001,13 @@ int lvk_seq_tokens(struct llama_context * ctx, int seq) {
 
 int lvk_rows_cols_active(struct llama_context * ctx, int n) {
     return ctx && !ctx->split && ctx->c.rows_cols(n) ? 1 : 0;
+}
+
+int lvk_decode_cu_active(struct llama_context * ctx) {
+    if (!ctx) return 0;
+    for (lvk::Context * c : ctx->stages())
+        if (!c->decode_cu()) return 0;
+    return 1;
 }
 
 int lvk_prompt_batched(struct llama_context * ctx, int n) {

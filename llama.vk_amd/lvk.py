@@ -142,6 +142,7 @@ _sig("lvk_cols41_store", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c
 _sig("lvk_cols41_resid", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p])
 _sig("lvk_cols41_swiglu", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p])
 _sig("lvk_rows_cols_active", C.c_int, [C.c_void_p, C.c_int])
+_sig("lvk_decode_cu_active", C.c_int, [C.c_void_p])
 _sig("lvk_prompt_batched", C.c_int, [C.c_void_p, C.c_int])
 _sig("lvk_prompt_weight_source", C.c_int, [C.c_int])
 _sig("lvk_host_tables", None, [u16p, u16p])
@@ -295,6 +296,11 @@ class Llama:
         """1 when a batched decode step of n rows on this context runs its matmuls through
         matvec_cols.hip (Q4_0) or matvec_cols41.hip (Q4_1) (lvk_rows_cols_active), else 0"""
         return int(lib.lvk_rows_cols_active(self.ctx, int(n)))
+
+    def decode_cu_active(self):
+        """1 when a single-token eval on this context runs every matrix on the CU-balanced decode
+        kernels (lvk_decode_cu_active), else 0"""
+        return int(lib.lvk_decode_cu_active(self.ctx))
 
     def prompt_batched(self, n):
         """1 when an n-token eval runs its matmuls as operand image + batched matmul (lvk_prompt_batched)"""

@@ -1,0 +1,111 @@
+"""Dev tool: single-sequence decode of the 13B- and 30B-shaped Q4_0 synthetic models on matvec_cu_long.hip
+against the generic kernels (LVK_DECODE_LONG=0, the route of the parent commit), with the 65B shape
+(k_mv_cu either way) as the control.
+usage: decode_long_speed.py [--layers N] [--repeats R] [--shapes a,b,...] [--out FILE]
+One process per leg, the legs alternating, R repeats (default 3).  A leg: the model of
+tools/seq_batch_speed.py cut to N layers (default 8; 0: the whole model), n_ctx 512, a 511-token prompt,
+then llama_eval of one token at 64 positions spread over 16..511, three passes after a warm-up of 8
+evals; the figure is the median eval (host clock around the call, which ends in the logits copy).  A
+fourth pass with the profiling classes on gives the device time per role and token.  Per shape the record
+holds the medians of the repeats, their spread (max - min) / median, and whether the new route beats the
+old by more than twice the larger spread (the rule for routing a row length by default).
+Writes profiles/decode_long_speed.json."""
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, 'llama.vk_amd'))
+import numpy as np
+import lvk
+from seq_batch_speed import CFG, N_CTX, spread, spread_pct
+
+
+def model_path(name, layers):
+    fn, cfg = CFG[name]
+    if layers:
+        fn, cfg = fn.replace('.bin', '-l%d.bin' % layers), dict(cfg, n_layer=layers)
+    path = os.path.join('/tmp/lvk_bench', fn)
+    if not os.path.exists(path):
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        lvk.gen_model(path, vocab=os.path.join(ROOT, 'tests', 'golden', 'vocab32000.bin'), **cfg)
+    return path
+
+
+def leg(path):
+    m = lvk.Llama(path, n_ctx=N_CTX)
+    m.eval(np.array([1] + [100 + (i * 7919) % 31000 for i in range(1, N_CTX - 1)], np.int32), 0)
+    pos = spread(64)
+    tok = [int(100 + (s * 104729) % 31000) for s in range(64)]
+    for p in pos[:8]:
+        m.eval([tok[0]], p)
+    ts = []
+    for _ in range(3):
+        for i, p in enumerate(pos):
+            t0 = time.perf_counter()
+            m.eval([tok[i]], p)
+            ts.append(time.perf_counter() - t0)
+    m.set_profiling(True)
+    m.reset_profile()
+    for i, p in enumerate(pos):
+        m.eval([tok[i]], p)
+    pr = m.profile()
+    rec = {'decode_cu_active': m.decode_cu_active(), 'median_ms': round(float(np.median(ts)) * 1e3, 4),
+           'tok_s': round(len(ts) / sum(ts), 1), 'weight_bytes': m.weight_bytes(),
+           'class_us_per_token': {k: round(v['ms'] / len(pos) * 1e3, 2) for k, v in pr.items() if v['launches']}}
+    m.close()
+    print('LEG ' + json.dumps(rec), flush=True)
+
+
+def main():
+    args = sys.argv[1:]
+    layers, repeats, out, shapes = 8, 3, os.path.join(ROOT, 'profiles', 'decode_long_speed.json'), ['13b-q4_0', '30b', '65b']
+    while args:
+        a = args.pop(0)
+        if a == '--leg':
+            return leg(args.pop(0))
+        if a == '--layers':
+            layers = int(args.pop(0))
+        elif a == '--repeats':
+            repeats = int(args.pop(0))
+        elif a == '--shapes':
+            shapes = args.pop(0).split(',')
+        elif a == '--out':
+            out = args.pop(0)
+    recs = json.load(open(out)) if os.path.exists(out) else []
+    for name in shapes:
+        path = model_path(name, layers)
+        legs = {'new': [], 'old': []}
+        for _ in range(repeats):
+            for which in ('new', 'old'):
+                env = dict(os.environ, LVK_DECODE_LONG='1' if which == 'new' else '0')
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), '--leg', path], env=env, capture_output=True,
+                                   text=True, timeout=600)
+                if r.returncode != 0:
+                    sys.exit('leg %s of %s failed (%d): %s' % (which, name, r.returncode, r.stdout + r.stderr))
+                legs[which].append(json.loads([l for l in r.stdout.splitlines() if l.startswith('LEG ')][-1][4:]))
+                print(name, which, legs[which][-1]['median_ms'], flush=True)
+        med = {w: [x['median_ms'] for x in legs[w]] for w in legs}
+        new, old = float(np.median(med['new'])), float(np.median(med['old']))
+        noise = max((max(v) - min(v)) for v in med.values())
+        mid = lambda w: sorted(legs[w], key=lambda x: x['median_ms'])[len(legs[w]) // 2]
+        rec = {'model': '%s synthetic%s' % (name, ' %d layers' % layers if layers else ''), 'n_ctx': N_CTX, 'repeats': repeats,
+               'weight_bytes': legs['new'][0]['weight_bytes'],
+               'new': {'decode_cu_active': legs['new'][0]['decode_cu_active'], 'median_ms': round(new, 4), 'repeats_ms': med['new'],
+                       'spread_pct': spread_pct(med['new']), 'class_us_per_token': mid('new')['class_us_per_token']},
+               'old_LVK_DECODE_LONG_0': {'decode_cu_active': legs['old'][0]['decode_cu_active'], 'median_ms': round(old, 4),
+                                         'repeats_ms': med['old'], 'spread_pct': spread_pct(med['old']),
+                                         'class_us_per_token': mid('old')['class_us_per_token']},
+               'old_over_new': round(old / new, 4), 'old_minus_new_ms': round(old - new, 4),
+               'twice_larger_spread_ms': round(2 * noise, 4), 'new_wins_by_rule': bool(old - new > 2 * noise)}
+        print(json.dumps(rec), flush=True)
+        recs = [r for r in recs if r['model'] != rec['model']] + [rec]
+        with open(out, 'w') as f:
+            json.dump(recs, f, indent=1)
+            f.write('\n')
+
+
+if __name__ == '__main__':
+    main()
