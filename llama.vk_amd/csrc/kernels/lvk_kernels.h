@@ -137,7 +137,7 @@ hipError_t launch_matvec_q41(const MvLaunch & L, int pro, int epi, hipStream_t s
 
 // single-token decode matvec, one workgroup per CU (matvec_cu.hip and, for the 13B / 30B row
 // lengths, matvec_cu_long.hip for Q4_0,
-// matvec_cu41.hip for Q4_1; F16 and F32 have one single-token kernel each, matvec_f16.hip and
+// matvec_cu41.hip and, for the 30B / 65B row lengths, matvec_cu41_long.hip for Q4_1; F16 and F32 have one single-token kernel each, matvec_f16.hip and
 // matvec_f32.hip, for every row length).  Row lengths compiled in: matvec_cu_supported(K, qtype).
 // Returns hipErrorNotSupported for anything else (the caller then uses launch_matvec).
 bool matvec_cu_supported(int K, int qtype = Q4_0);

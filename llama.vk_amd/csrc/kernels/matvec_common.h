@@ -14,6 +14,10 @@ hipError_t launch_matvec_cu41(const MvLaunch & L, int pro, int epi, hipStream_t 
 // env LVK_DECODE_LONG=0)
 bool matvec_cu_long_supported(int K);
 hipError_t launch_matvec_cu_long(const MvLaunch & L, int pro, int epi, hipStream_t s);
+// the Q4_1 row lengths of LLaMA 30B / 65B (matvec_cu41_long.hip: 6656 / 17920, 8192 / 22016; none with
+// env LVK_DECODE_LONG=0)
+bool matvec_cu41_long_supported(int K);
+hipError_t launch_matvec_cu41_long(const MvLaunch & L, int pro, int epi, hipStream_t s);
 
 namespace mv {
 

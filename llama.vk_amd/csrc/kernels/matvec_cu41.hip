@@ -280,10 +280,15 @@ hipError_t go(const Cu41Params & P, hipStream_t s) {
 
 }  // namespace
 
-bool matvec_cu41_supported(int K) { return K == 4096 || K == 5120 || K == 11008 || K == 13824; }
+// row lengths compiled in: the LLaMA 7B and 13B Q4_1 shapes here, the 30B and 65B ones (6656 / 17920,
+// 8192 / 22016) in matvec_cu41_long.hip
+bool matvec_cu41_supported(int K) {
+    return K == 4096 || K == 5120 || K == 11008 || K == 13824 || matvec_cu41_long_supported(K);
+}
 
 hipError_t launch_matvec_cu41(const MvLaunch & L, int pro, int epi, hipStream_t s) {
     if (L.w.qtype != Q4_1 || L.n_tokens != 1 || L.w.M % 8) return hipErrorNotSupported;
+    if (matvec_cu41_long_supported(L.w.K)) return launch_matvec_cu41_long(L, pro, epi, s);
     if (!mv_inputs_set(L, pro)) return hipErrorInvalidValue;
     Cu41Params P{};
     mv_fill(P, L, true);

@@ -1,7 +1,8 @@
 """Dev tool: single-sequence decode of the 13B- and 30B-shaped Q4_0 synthetic models on matvec_cu_long.hip
 against the generic kernels (LVK_DECODE_LONG=0, the route of the parent commit), with the 65B shape
-(k_mv_cu either way) as the control.
-usage: decode_long_speed.py [--layers N] [--repeats R] [--shapes a,b,...] [--out FILE]
+(k_mv_cu either way) as the control; with --wtype q4_1 the 30B- and 65B-shaped Q4_1 models on
+matvec_cu41_long.hip against the same switch (profiles/decode_long41_speed.json).
+usage: decode_long_speed.py [--wtype q4_0|q4_1] [--layers N] [--repeats R] [--shapes a,b,...] [--out FILE]
 One process per leg, the legs alternating, R repeats (default 3).  A leg: the model of
 tools/seq_batch_speed.py cut to N layers (default 8; 0: the whole model), n_ctx 512, a 511-token prompt,
 then llama_eval of one token at 64 positions spread over 16..511, three passes after a warm-up of 8
@@ -23,8 +24,10 @@ import lvk
 from seq_batch_speed import CFG, N_CTX, spread, spread_pct
 
 
-def model_path(name, layers):
+def model_path(name, layers, wtype='q4_0'):
     fn, cfg = CFG[name]
+    if wtype == 'q4_1':         # the same shape and seed as a Q4_1 file
+        fn, cfg = fn.replace('q4_0', 'q4_1'), dict(cfg, ftype=3)
     if layers:
         fn, cfg = fn.replace('.bin', '-l%d.bin' % layers), dict(cfg, n_layer=layers)
     path = os.path.join('/tmp/lvk_bench', fn)
@@ -61,7 +64,7 @@ def leg(path):
 
 def main():
     args = sys.argv[1:]
-    layers, repeats, out, shapes = 8, 3, os.path.join(ROOT, 'profiles', 'decode_long_speed.json'), ['13b-q4_0', '30b', '65b']
+    layers, repeats, out, shapes, wtype = 8, 3, None, None, 'q4_0'
     while args:
         a = args.pop(0)
         if a == '--leg':
@@ -74,9 +77,16 @@ def main():
             shapes = args.pop(0).split(',')
         elif a == '--out':
             out = args.pop(0)
+        elif a == '--wtype':
+            wtype = args.pop(0)
+    if wtype not in ('q4_0', 'q4_1'):
+        sys.exit('--wtype: q4_0 or q4_1')
+    q41 = wtype == 'q4_1'
+    out = out or os.path.join(ROOT, 'profiles', 'decode_long41_speed.json' if q41 else 'decode_long_speed.json')
+    shapes = shapes or (['30b', '65b'] if q41 else ['13b-q4_0', '30b', '65b'])
     recs = json.load(open(out)) if os.path.exists(out) else []
     for name in shapes:
-        path = model_path(name, layers)
+        path = model_path(name, layers, wtype)
         legs = {'new': [], 'old': []}
         for _ in range(repeats):
             for which in ('new', 'old'):
@@ -91,7 +101,7 @@ def main():
         new, old = float(np.median(med['new'])), float(np.median(med['old']))
         noise = max((max(v) - min(v)) for v in med.values())
         mid = lambda w: sorted(legs[w], key=lambda x: x['median_ms'])[len(legs[w]) // 2]
-        rec = {'model': '%s synthetic%s' % (name, ' %d layers' % layers if layers else ''), 'n_ctx': N_CTX, 'repeats': repeats,
+        rec = {'model': '%s%s synthetic%s' % (name, ' q4_1' if q41 else '', ' %d layers' % layers if layers else ''), 'n_ctx': N_CTX, 'repeats': repeats,
                'weight_bytes': legs['new'][0]['weight_bytes'],
                'new': {'decode_cu_active': legs['new'][0]['decode_cu_active'], 'median_ms': round(new, 4), 'repeats_ms': med['new'],
                        'spread_pct': spread_pct(med['new']), 'class_us_per_token': mid('new')['class_us_per_token']},
@@ -99,7 +109,7 @@ def main():
                                          'repeats_ms': med['old'], 'spread_pct': spread_pct(med['old']),
                                          'class_us_per_token': mid('old')['class_us_per_token']},
                'old_over_new': round(old / new, 4), 'old_minus_new_ms': round(old - new, 4),
-               'twice_larger_spread_ms': round(2 * noise, 4), 'new_wins_by_rule': bool(old - new > 2 * noise)}
+               'larger_spread_ms': round(noise, 4), 'twice_larger_spread_ms': round(2 * noise, 4), 'new_wins_by_rule': bool(old - new > 2 * noise)}
         print(json.dumps(rec), flush=True)
         recs = [r for r in recs if r['model'] != rec['model']] + [rec]
         with open(out, 'w') as f:
