@@ -155,8 +155,8 @@ LVK_API int lvk_attention_rows(int type, const uint16_t * kc, const uint16_t * v
  * type is the weight type (0 f32, 1 f16, 2 Q4_0, 3 Q4_1).  path selects the launcher:
  *   0  what a context chooses for this n (n == 1: launch_matvec_auto; a batch: the generic kernels
  *      for Q4 below 16 tokens, else the batched route)
- *   1  launch_matvec_cu (n == 1: matvec_cu.hip / matvec_cu_long.hip / matvec_cu41.hip / matvec_cu41_long.hip, or
- *      the one f16 / f32 matvec)
+ *   1  launch_matvec_cu (n == 1: matvec_cu.hip / matvec_cu41.hip, for the long rows the chunk stream of
+ *      matvec_cu_stream.h as matvec_cu_long.hip / matvec_cu41_long.hip, or the one f16 / f32 matvec)
  *   2  launch_matvec (the generic kernels of matvec_q4.hip / matvec_q41.hip, any n; f16 / f32: n == 1)
  *   3  the batched route: launch_act (or launch_actq_to_image) + launch_mm
  * Every argument is checked on the host before anything is uploaded (k % 256 == 0, 1 <= n <= 4096,
@@ -241,7 +241,8 @@ LVK_API int lvk_rows_cols_active(struct llama_context * ctx, int n);
 /* 1 when a single-token eval on this context (every stage of a split) runs every matrix through
  * launch_matvec_cu, the CU-balanced decode kernels: a Q4_0 model with the row lengths 4096 / 11008,
  * 5120 / 13824, 6656 / 17920 or 8192 / 22016, a Q4_1 model with those matvec_cu41.hip (4096 / 11008,
- * 5120 / 13824) or matvec_cu41_long.hip (6656 / 17920, 8192 / 22016) has, an f16 or f32 model, every
+ * 5120 / 13824) or the chunk stream's Q4_1 format in matvec_cu41_long.hip (6656 / 17920, 8192 /
+ * 22016) has, an f16 or f32 model, every
  * matrix a whole number of 8-row groups; else 0 (the generic kernels for some or all).  Env
  * LVK_DECODE_LONG=0 (read once per process) keeps Q4_0 5120 / 13824 and 6656 / 17920 and Q4_1
  * 6656 / 17920 and 8192 / 22016 on the generic kernels. */

@@ -135,9 +135,10 @@ hipError_t launch_matvec(const MvLaunch & L, int pro, int epi, hipStream_t s);
 // the same for Q4_1 weights (matvec_q41.hip)
 hipError_t launch_matvec_q41(const MvLaunch & L, int pro, int epi, hipStream_t s);
 
-// single-token decode matvec, one workgroup per CU (matvec_cu.hip and, for the 13B / 30B row
-// lengths, matvec_cu_long.hip for Q4_0,
-// matvec_cu41.hip and, for the 30B / 65B row lengths, matvec_cu41_long.hip for Q4_1; F16 and F32 have one single-token kernel each, matvec_f16.hip and
+// single-token decode matvec, one workgroup per CU (matvec_cu.hip for Q4_0 and matvec_cu41.hip for
+// Q4_1; the 13B / 30B row lengths of Q4_0 and the 30B / 65B ones of Q4_1 run the chunk stream of
+// matvec_cu_stream.h, as k_mv_cu_long in matvec_cu_long.hip and k_mv_cu41_long in
+// matvec_cu41_long.hip; F16 and F32 have one single-token kernel each, matvec_f16.hip and
 // matvec_f32.hip, for every row length).  Row lengths compiled in: matvec_cu_supported(K, qtype).
 // Returns hipErrorNotSupported for anything else (the caller then uses launch_matvec).
 bool matvec_cu_supported(int K, int qtype = Q4_0);

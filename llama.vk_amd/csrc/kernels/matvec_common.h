@@ -2,6 +2,7 @@
 // in LDS with their prologue pieces (reference Q4_0 / Q4_1 quantizers), the octet reduce and
 // the epilogues.
 #pragma once
+#include <cstdlib>
 #include "lvk_device.h"
 #include "lvk_kernels.h"
 
@@ -297,6 +298,75 @@ inline void mv_fill(MvArgs & A, const MvLaunch & L, bool at_tok0) {
     A.q16 = L.q16; A.kc = L.kc; A.vc = L.vc; A.rope = L.rope.cs;
     A.n_embd = L.n_embd; A.head_dim = L.head_dim; A.n_ctx = L.n_ctx; A.kv32 = L.kv32;
     A.silu_tab = L.silu_tab;
+}
+
+// ---- what the CU-balanced single-token kernels share (k_mv_cu, k_mv_cu41 and the chunk stream of
+// matvec_cu_stream.h)
+
+// The weight images lead the parameter block: the kernel's first scalar loads fetch what the row-group
+// split and the weight addresses need (profiles/mv_args_kernel_resources.md: with the images last the
+// prologue inputs were waited for ahead of the weight address arithmetic)
+struct CuImages {
+    const uint4 * nib;          // [G][NC][4 sub][64]
+    const float4 * scl;         // [G][NC][64]
+    int G;                      // row groups (M / 8)
+};
+struct Cu41Images {
+    const uint4 * nib;          // [G][NC][4 sub][64]
+    const float4 * scl;         // [G][NC][2][64]: d, then m
+    const uint4 * wsum;         // [G][NC][64]: even-chain weight sums (lvk_kernels.h q41_wsum)
+    int G;                      // row groups (M / 8)
+};
+struct CuParams : CuImages, MvArgs {};
+struct Cu41Params : Cu41Images, MvArgs {};
+
+// the parameter block of a single-token launch (inputs advanced to token L.tok0)
+inline void cu_fill(CuParams & P, const MvLaunch & L) {
+    mv_fill(P, L, true);
+    P.nib = L.w.nib;
+    P.scl = (const float4 *) L.w.scl;
+    P.G = L.w.M / 8;
+}
+inline void cu_fill(Cu41Params & P, const MvLaunch & L) {
+    mv_fill(P, L, true);
+    P.nib = L.w.nib;
+    P.scl = (const float4 *) L.w.scl;
+    P.wsum = q41_wsum(L.w);
+    P.G = L.w.M / 8;
+}
+
+// per-wave block-product tables in LDS (Q4_0: s = dw * dx; Q4_1: four, s = dx*dy, dx*my, mx*dy, mx*my)
+// of 8 rows x 32 blocks: SPL floats a table, SWF the four of Q4_1.  The row stride SRS is padded to 40
+// floats so the 8 rows start on banks 0, 40, 16, 56, 32, 8, 48, 24 of the 64: the per-row broadcast
+// float4 reads and the lane stores are bank-conflict free (a 32-float stride put rows 0/2/4/6 on the
+// same banks).  In a namespace of their own: the columns kernels, which also use namespace mv, have
+// slices of the same names (matvec_cols_common.h)
+namespace cu_lds {
+constexpr int SRS = 40, SPL = 8 * SRS, SWF = 4 * SPL;
+}
+
+// workgroup bid of nwg owns the row groups [row_group0(bid), row_group0(bid + 1)) of the G: every CU
+// streams the same bytes, +-1 row group
+__device__ __forceinline__ int row_group0(int bid, int nwg, int G) {
+    return (int) ((unsigned) bid * (unsigned) G / (unsigned) nwg);      // G * n_cu < 2^32
+}
+
+// LVK_DECODE_LONG=0 (read once per process) keeps the long row lengths on the generic kernels, for A/B runs
+inline bool decode_long_on() {
+    static const bool on = [] { const char * e = getenv("LVK_DECODE_LONG"); return !e || atoi(e) != 0; }();
+    return on;
+}
+
+// The QKV epilogue's position, loaded ahead of the prologue inputs (vmcnt retires in order: the
+// inputs' wait covers it), so that the RoPE pair can be loaded at a row group's start (mv_pre_epi).
+// An atomic load: a plain one is sunk to its use; a scalar one sinks too and then holds up the
+// prologue's first barrier, whose lgkmcnt wait covers it.
+template <int EPI>
+__device__ __forceinline__ int mv_pos0(const MvArgs & P) {
+    if constexpr (EPI == EPI_QKV)
+        return __hip_atomic_load((const __attribute__((address_space(1))) int *) &P.sp->n_past, __ATOMIC_RELAXED,
+                                 __HIP_MEMORY_SCOPE_AGENT);
+    return 0;
 }
 
 // the input that prologue pro reads must be there

@@ -25,6 +25,7 @@ namespace lvk {
 
 namespace {
 using namespace mv;
+using namespace mv::cu_lds;
 
 #ifdef LVK_PROBE_TIMING   // dev probe builds only: per-wave s_memtime trace
 __device__ unsigned long long g_trace[256 * 16 * 64];
@@ -36,15 +37,6 @@ __device__ unsigned long long g_trace[256 * 16 * 64];
 #else
 #define LVK_T(ev) do { } while (0)
 #endif
-
-// (the images lead the block: the kernel's first scalar loads fetch what the row-group split and
-// the weight addresses need)
-struct CuImages {
-    const uint4 * nib;
-    const float4 * scl;
-    int G;                      // row groups (M / 8)
-};
-struct CuParams : CuImages, MvArgs {};
 
 // order of the prologue and the first weight loads (k_mv_cu PF; the values are what the sweep
 // build's LVK_MV_PF takes)
@@ -58,11 +50,6 @@ enum PfOrder : int {
                             // wave's issue, which the memory system throttles to the return rate
                             // once the CU's queue is full)
 };
-
-// per-wave block-scale table s = dw * dx in LDS (two buffers, 8 rows x 32 blocks): the row
-// stride is padded to 40 floats so the rows start on banks 0, 40, 16, 56, 32, 8, 48, 24 of
-// the 64 and the per-row broadcast float4 reads are bank-conflict free
-constexpr int SRS = 40, SPL = 8 * SRS;
 
 // the workgroup body (bid of nwg workgroups)
 template <int NW, int NP, int D, int PRO, int EPI, int KT, int PF>
@@ -136,19 +123,11 @@ __device__ __forceinline__ void mv_cu_run(const CuParams & P, const int bid, con
     // ---- compute waves
     const int j = lane & 7;
     const int r = lane >> 3;
-    const int g0 = (int) ((unsigned) bid * (unsigned) P.G / (unsigned) nwg);     // G * n_cu < 2^32
-    const int g1 = (int) ((unsigned) (bid + 1) * (unsigned) P.G / (unsigned) nwg);
+    const int g0 = row_group0(bid, nwg, P.G), g1 = row_group0(bid + 1, nwg, P.G);
     const int ng = max(0, (g1 - g0 - wave + NW - 1) / NW);      // row groups of this wave
     if (NP > 0 && ng == 0) { __builtin_amdgcn_s_barrier(); __syncthreads(); return; }
     int gc = min(g0 + wave, P.G - 1);
-    // the QKV epilogue's position, loaded here ahead of the prologue inputs (vmcnt retires in
-    // order: the inputs' wait covers it), so that the RoPE pair can be loaded at a row group's
-    // start (mv_pre_epi).  An atomic load: a plain one is sunk to its use; a scalar one sinks
-    // too and then holds up the prologue's first barrier, whose lgkmcnt wait covers it.
-    [[maybe_unused]] int pos0 = 0;
-    if constexpr (EPI == EPI_QKV)
-        pos0 = __hip_atomic_load((const __attribute__((address_space(1))) int *) &P.sp->n_past, __ATOMIC_RELAXED,
-                                 __HIP_MEMORY_SCOPE_AGENT);
+    [[maybe_unused]] const int pos0 = mv_pos0<EPI>(P);          // ahead of the prologue inputs
 
     // NP == 0: the compute waves build the activation table themselves; its
     // inputs are issued first (vmcnt retires in order)
@@ -437,10 +416,7 @@ hipError_t launch_matvec_cu(const MvLaunch & L, int pro, int epi, hipStream_t s)
     if (matvec_cu_long_supported(L.w.K)) return launch_matvec_cu_long(L, pro, epi, s);
     if (!mv_inputs_set(L, pro)) return hipErrorInvalidValue;
     CuParams P{};
-    mv_fill(P, L, true);
-    P.nib = L.w.nib;
-    P.scl = (const float4 *) L.w.scl;
-    P.G = L.w.M / 8;
+    cu_fill(P, L);
     const int K = L.w.K;
 #ifdef LVK_PROBE_SWEEP   // dev probe builds only: LVK_CFG selects a launch shape
     {

@@ -25,21 +25,7 @@ namespace lvk {
 
 namespace {
 using namespace mv;
-
-// (the images lead the block, as in matvec_cu.hip)
-struct Cu41Images {
-    const uint4 * nib;
-    const float4 * scl;         // [G][NC][2][64]: d, then m
-    const uint4 * wsum;         // [G][NC][64]: even-chain weight sums (lvk_kernels.h q41_wsum)
-    int G;                      // row groups (M / 8)
-};
-struct Cu41Params : Cu41Images, MvArgs {};
-
-// per-wave block-product tables in LDS: 4 tables (s, dx*my, mx*dy, mx*my) of 8 rows x 32
-// blocks; the row stride is padded to 40 floats so the 8 rows start on banks 0, 40, 16, 56,
-// 32, 8, 48, 24 (64 banks): the per-row broadcast float4 reads and the lane stores are
-// bank-conflict free (a 32-float stride put rows 0/2/4/6 on the same banks)
-constexpr int SRS = 40, SPL = 8 * SRS, SWF = 4 * SPL;
+using namespace mv::cu_lds;
 
 // SPLIT: only chunk 0 goes out before the activation table, chunks 1..D-1 after the workgroup
 // barrier (the barriers wait for the slowest wave's issue, which the memory system throttles
@@ -68,18 +54,10 @@ __global__ __launch_bounds__(NW * 64) void k_mv_cu41(Cu41Params P) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int j = lane & 7;
     const int r = lane >> 3;
-    const int nwg = gridDim.x;
-    // this CU's row groups [g0, g1)
-    const int g0 = (int) (blockIdx.x * (unsigned) P.G / (unsigned) nwg);
-    const int g1 = (int) ((blockIdx.x + 1) * (unsigned) P.G / (unsigned) nwg);
+    const int g0 = row_group0(blockIdx.x, gridDim.x, P.G), g1 = row_group0(blockIdx.x + 1, gridDim.x, P.G);
     const int ng = max(0, (g1 - g0 - wave + NW - 1) / NW);      // row groups of this wave
     int gc = min(g0 + wave, P.G - 1);
-    // the QKV epilogue's position, loaded ahead of the inputs so that the RoPE pair can be loaded at
-    // a row group's start (mv_pre_epi)
-    [[maybe_unused]] int pos0 = 0;
-    if constexpr (EPI == EPI_QKV)
-        pos0 = __hip_atomic_load((const __attribute__((address_space(1))) int *) &P.sp->n_past, __ATOMIC_RELAXED,
-                                 __HIP_MEMORY_SCOPE_AGENT);
+    [[maybe_unused]] const int pos0 = mv_pos0<EPI>(P);          // ahead of the inputs
 
     // activation inputs first (vmcnt retires in order)
     constexpr bool FPRO = (PRO == PRO_NORM || PRO == PRO_ACTF);
@@ -291,11 +269,7 @@ hipError_t launch_matvec_cu41(const MvLaunch & L, int pro, int epi, hipStream_t 
     if (matvec_cu41_long_supported(L.w.K)) return launch_matvec_cu41_long(L, pro, epi, s);
     if (!mv_inputs_set(L, pro)) return hipErrorInvalidValue;
     Cu41Params P{};
-    mv_fill(P, L, true);
-    P.nib = L.w.nib;
-    P.scl = (const float4 *) L.w.scl;
-    P.wsum = q41_wsum(L.w);
-    P.G = L.w.M / 8;
+    cu_fill(P, L);
     const int K = L.w.K;
 #ifdef LVK_PROBE_SWEEP   // dev probe builds only: LVK_CFG41 selects a launch shape (waves, prefetch depth)
     {

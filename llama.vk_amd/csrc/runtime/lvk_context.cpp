@@ -278,7 +278,9 @@ bool Context::rows_cols(int n) const {
 // row lengths of the model are compiled in for its type (matvec_cu_supported; for Q4_0 13B / 30B and Q4_1 30B / 65B not with
 // env LVK_DECODE_LONG=0) and every matrix is whole row groups.  enqueue_forward's single-token branch
 // follows the same two tests through launch_matvec_auto and ffn_f32.  matvec_cu_supported does not know the
-// role: matvec_cu_long.hip has the n_embd roles at 5120 / 6656 and the n_ff roles at 13824 / 17920 only (matvec_cu41_long.hip: 6656 / 8192 and 17920 / 22016), so
+// role: the chunk stream's role table (matvec_cu_stream.h) has the n_embd roles at a format's two n_embd
+// lengths and the n_ff roles at its two n_ff lengths only (matvec_cu_long.hip: 5120 / 6656 and 13824 /
+// 17920; matvec_cu41_long.hip: 6656 / 8192 and 17920 / 22016), so
 // a model with n_embd 13824 would report 1 while its QKV takes the generic kernel.  No LLaMA file has such a
 // shape (n_ff follows from n_embd).
 bool Context::decode_cu() const {

@@ -3,6 +3,7 @@ against the generic kernels (LVK_DECODE_LONG=0, the route of the parent commit),
 (k_mv_cu either way) as the control; with --wtype q4_1 the 30B- and 65B-shaped Q4_1 models on
 matvec_cu41_long.hip against the same switch (profiles/decode_long41_speed.json).
 usage: decode_long_speed.py [--wtype q4_0|q4_1] [--layers N] [--repeats R] [--shapes a,b,...] [--out FILE]
+                            [--libs PARENT.so NEW.so]
 One process per leg, the legs alternating, R repeats (default 3).  A leg: the model of
 tools/seq_batch_speed.py cut to N layers (default 8; 0: the whole model), n_ctx 512, a 511-token prompt,
 then llama_eval of one token at 64 positions spread over 16..511, three passes after a warm-up of 8
@@ -10,7 +11,11 @@ evals; the figure is the median eval (host clock around the call, which ends in 
 fourth pass with the profiling classes on gives the device time per role and token.  Per shape the record
 holds the medians of the repeats, their spread (max - min) / median, and whether the new route beats the
 old by more than twice the larger spread (the rule for routing a row length by default).
-Writes profiles/decode_long_speed.json."""
+Writes profiles/decode_long_speed.json.
+With --libs the two legs are two builds of the library (LVK_LIB) on the same route instead of the two
+switch settings, for a refactor: per shape and per role the record holds each build's median device time
+over the repeats with its spread, and whether the new build is slower than the parent's by more than
+twice the larger of the two spreads (--out is then required)."""
 import json
 import os
 import subprocess
@@ -62,9 +67,32 @@ def leg(path):
     print('LEG ' + json.dumps(rec), flush=True)
 
 
+LIBS_WHAT = ('tools/decode_long_speed.py --libs PARENT NEW: two builds of the library on the same route, shapes cut to 8 layers, '
+             'one process per leg, parent and new alternating, medians of the repeats; per role the device time per token; '
+             'new_slower_by_rule: new - parent > twice the larger of the two spreads (max - min of the repeats)')
+
+
+def libs_record(name, q41, layers, repeats, legs, med):
+    """two builds on the same route: per role the medians of the repeats, their spreads, and the rule"""
+    side = lambda w: {'decode_cu_active': legs[w][0]['decode_cu_active'], 'median_ms': round(float(np.median(med[w])), 4),
+                      'repeats_ms': med[w], 'spread_ms': round(max(med[w]) - min(med[w]), 4)}
+    roles = {}
+    for k in legs['new'][0]['class_us_per_token']:
+        v = {w: [x['class_us_per_token'][k] for x in legs[w]] for w in legs}
+        m = {w: float(np.median(v[w])) for w in v}
+        noise = max(max(x) - min(x) for x in v.values())
+        roles[k] = {'parent_us': round(m['old'], 2), 'new_us': round(m['new'], 2), 'parent_repeats_us': v['old'],
+                    'new_repeats_us': v['new'], 'new_minus_parent_us': round(m['new'] - m['old'], 2),
+                    'twice_larger_spread_us': round(2 * noise, 2), 'new_slower_by_rule': bool(m['new'] - m['old'] > 2 * noise)}
+    return {'model': '%s%s synthetic%s' % (name, ' q4_1' if q41 else '', ' %d layers' % layers if layers else ''),
+            'n_ctx': N_CTX, 'repeats': repeats, 'weight_bytes': legs['new'][0]['weight_bytes'], 'parent': side('old'),
+            'new': side('new'), 'roles_device_us_per_token': roles,
+            'any_role_slower_by_rule': any(r['new_slower_by_rule'] for r in roles.values())}
+
+
 def main():
     args = sys.argv[1:]
-    layers, repeats, out, shapes, wtype = 8, 3, None, None, 'q4_0'
+    layers, repeats, out, shapes, wtype, libs = 8, 3, None, None, 'q4_0', None
     while args:
         a = args.pop(0)
         if a == '--leg':
@@ -79,18 +107,25 @@ def main():
             out = args.pop(0)
         elif a == '--wtype':
             wtype = args.pop(0)
+        elif a == '--libs':
+            libs = {'old': os.path.abspath(args.pop(0)), 'new': os.path.abspath(args.pop(0))}
     if wtype not in ('q4_0', 'q4_1'):
         sys.exit('--wtype: q4_0 or q4_1')
+    if libs and not out:
+        sys.exit('--libs needs --out')
     q41 = wtype == 'q4_1'
     out = out or os.path.join(ROOT, 'profiles', 'decode_long41_speed.json' if q41 else 'decode_long_speed.json')
     shapes = shapes or (['30b', '65b'] if q41 else ['13b-q4_0', '30b', '65b'])
-    recs = json.load(open(out)) if os.path.exists(out) else []
+    recs = json.load(open(out)) if os.path.exists(out) and not libs else []
+    doc = json.load(open(out)) if os.path.exists(out) and libs else {'what': LIBS_WHAT, 'shapes': []}
     for name in shapes:
         path = model_path(name, layers, wtype)
         legs = {'new': [], 'old': []}
         for _ in range(repeats):
             for which in ('new', 'old'):
-                env = dict(os.environ, LVK_DECODE_LONG='1' if which == 'new' else '0')
+                env = dict(os.environ, LVK_DECODE_LONG='1' if which == 'new' or libs else '0')
+                if libs:
+                    env['LVK_LIB'] = libs[which]
                 r = subprocess.run([sys.executable, os.path.abspath(__file__), '--leg', path], env=env, capture_output=True,
                                    text=True, timeout=600)
                 if r.returncode != 0:
@@ -98,6 +133,14 @@ def main():
                 legs[which].append(json.loads([l for l in r.stdout.splitlines() if l.startswith('LEG ')][-1][4:]))
                 print(name, which, legs[which][-1]['median_ms'], flush=True)
         med = {w: [x['median_ms'] for x in legs[w]] for w in legs}
+        if libs:
+            rec = libs_record(name, q41, layers, repeats, legs, med)
+            print(json.dumps(rec), flush=True)
+            doc['shapes'] = [r for r in doc['shapes'] if r['model'] != rec['model']] + [rec]
+            with open(out, 'w') as f:
+                json.dump(doc, f, indent=1)
+                f.write('\n')
+            continue
         new, old = float(np.median(med['new'])), float(np.median(med['old']))
         noise = max((max(v) - min(v)) for v in med.values())
         mid = lambda w: sorted(legs[w], key=lambda x: x['median_ms'])[len(legs[w]) // 2]
